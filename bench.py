@@ -4,6 +4,7 @@ maxdisp 192 (k=4, input_scale=0), forward + one online-adaptation step, syntheti
 1..8 MI355X (one process per GPU, RCCL gradient all-reduce).
 
   python bench.py --gpus 1 --steps 20 --warmup 5
+  python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR    (+ the last timed step's results as DIR/*.npy)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
       --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -58,7 +59,13 @@ def parse():
                   "per-replica statistics")
   ap.add_argument("--no-graph", action="store_true", help="launch the ~130 kernels of a step eagerly instead of "
                                                           "replaying a captured hipGraph (single GPU only)")
-  return ap.parse_args()
+  ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed "
+                  "adaptation step returned (loss, FCS, its EMA, every output map and the coarse arg-max) as DIR/<name>.npy "
+                  "(rank 0; float32, float64 kept; at most 64 MB in all, a larger map is a fixed, seeded sample of its elements)")
+  args = ap.parse_args()
+  if args.steps < 1:
+    ap.error("--steps must be at least 1")
+  return args
 
 
 def log(msg):
@@ -103,14 +110,15 @@ def model_flops(H, W, k, maxdisp):
   return {"feature_towers": 2 * feat, "aggregation": agg, "refinement": refine, "forward": 2 * feat + agg + refine}
 
 
-def timed(fn, steps, world):
-  """barrier + synchronize, K calls, synchronize + barrier; MAX over ranks (seconds)."""
+def timed(fn, steps, world, last=None):
+  """barrier + synchronize, K calls, synchronize + barrier; MAX over ranks (seconds).  `last` (a list) receives what the
+  K-th call returned."""
   if world > 1:
     dist.barrier()
   torch.cuda.synchronize()
   t0 = time.perf_counter()
   for _ in range(steps):
-    fn()
+    r = fn()
   torch.cuda.synchronize()
   if world > 1:
     dist.barrier()
@@ -119,7 +127,45 @@ def timed(fn, steps, world):
     t = torch.tensor([dt], dtype=torch.float64, device="cuda")
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     dt = float(t)
+  if last is not None:
+    last.append(r)
   return dt
+
+
+DUMP_BYTES = 64 << 20
+DUMP_SEED = 20211
+
+
+def dump_outputs(dirname, res):
+  """Writes a step result ({"loss", "fcs", "fcs_smoothed", "outputs": {name: map}}, as OnlineAdapter.step returns it) as
+  DIR/<name>.npy, "/" in a name becoming ".".  Called right after the timed region: a replayed graph returns its own static
+  buffers, which the next step overwrites.  float64 stays float64, everything else is written as float32 (the arg-max
+  indices are exact in it).  The budget is shared out from the smallest array up: an array over its share is replaced by a
+  sample of that many of its elements (flat indices drawn without replacement by a generator seeded with DUMP_SEED, in
+  ascending order), so two runs with the same arguments sample the same elements."""
+  import numpy as np
+  named = [("loss", res["loss"]), ("fcs", res["fcs"]), ("fcs_smoothed", res["fcs_smoothed"])]
+  for key in sorted(res["outputs"]):
+    t = res["outputs"][key]
+    named.append(("outputs." + key.replace("/", "."), t))
+    if getattr(t, "_as_argmax", None) is not None:
+      named.append(("outputs." + key.replace("/", ".") + ".argmax", t._as_argmax))
+  arrays = []
+  for name, t in named:
+    a = t.detach().cpu().numpy()
+    arrays.append((name, a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)))
+  os.makedirs(dirname, exist_ok=True)
+  left, sampled = DUMP_BYTES, []
+  for i, (name, a) in enumerate(sorted(arrays, key=lambda na: (na[1].nbytes, na[0]))):
+    share = left // (len(arrays) - i) // a.itemsize
+    if a.size > share:
+      idx = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, size=share, replace=False))
+      a = a.reshape(-1)[idx]
+      sampled.append(name)
+    np.save(os.path.join(dirname, name + ".npy"), a)
+    left -= a.nbytes
+  log("dumped %d arrays of the last timed step to %s (%.1f MB%s)" % (
+      len(arrays), dirname, (DUMP_BYTES - left) / 2.0 ** 20, "; sampled: " + ", ".join(sampled) if sampled else ""))
 
 
 def cpu_share():
@@ -381,7 +427,10 @@ def main():
       adapter.step(step_l, step_r)
     torch.cuda.synchronize()
     log("step captured into a hipGraph")
-  t_adapt = timed(lambda: adapter.step(step_l, step_r), args.steps, world)
+  last = []
+  t_adapt = timed(lambda: adapter.step(step_l, step_r), args.steps, world, last)
+  if args.dump_outputs and rank == 0:
+    dump_outputs(args.dump_outputs, last[0])
 
   # Roofline leg: per-launch durations of the dominant kernels from HIP events on the launch stream.
   # Events cannot bracket nodes inside a graph replay, so with --graph the same K steps are run once

@@ -9,7 +9,8 @@
      194 x3, 200 x3; 21260 is not countable, see NOT_COUNTABLE) are re-counted from the reference's split manifests with the PRODUCT's StereoDataset /
      utils.dataset_utils.read_lines; the counts, the expected numbers and each manifest's sha256 go to
      tests/golden/dataset/split_lengths.json.  The three KITTI-2015 manifests (200 lines each, the benchmark's data set)
-     are copied as fixture data so that the length test also runs where /root/reference does not exist.
+     are copied as fixture data, the other nine xz-compressed (splits_xz/, ~170 kB), so that the length test counts every
+     manifest without the reference tree.
 
 The reference's dataset MODULE (datasets/stereo_dataset.py, utils/dataset_utils.py) still cannot be imported here
 (torchvision, imageio, cv2 are absent), so crop / flip / pyramid logic stays pinned by the oracle's reading alone."""
@@ -96,6 +97,19 @@ def main():
   dst = os.path.join(OUT, "splits", "kitti_stereo_2015"); os.makedirs(dst, exist_ok=True)
   for sub in ("train", "val", "test"):
     shutil.copyfile(os.path.join(splits, "kitti_stereo_2015", "%s_lines.txt" % sub), os.path.join(dst, "%s_lines.txt" % sub))
+  compress_other_manifests(splits)
+
+
+def compress_other_manifests(splits):
+  """The manifests of EXPECTED other than KITTI-2015 (up to 3 MB each as text), xz-compressed under dataset/splits_xz/."""
+  import lzma
+  for _, split, subsplit, _ in EXPECTED:
+    if split == "kitti_stereo_2015":
+      continue
+    dst = os.path.join(OUT, "splits_xz", split); os.makedirs(dst, exist_ok=True)
+    raw = open(os.path.join(splits, split, "%s_lines.txt" % subsplit), "rb").read()
+    with open(os.path.join(dst, "%s_lines.txt.xz" % subsplit), "wb") as f:
+      f.write(lzma.compress(raw, preset=9 | lzma.PRESET_EXTREME))
 
 
 if __name__ == "__main__":

@@ -146,12 +146,13 @@ def test_pfm_reader_matches_the_reference_reader_on_its_own_sample():
   assert torch.equal(dorc.load_disp("SceneFlowFlying", path), t)
 
 
-def test_split_lengths_asserted_by_the_reference_test():
+def test_split_lengths_asserted_by_the_reference_test(tmp_path):
   """test/test_stereo_dataset.py:24-97 of the reference asserts the data set lengths; the KITTI-2015 manifests (the
-  benchmark's data set) are committed as fixture data, the others are re-counted from /root/reference where it exists
-  and otherwise checked against the counts recorded (with the manifests' sha256) when the fixture was made."""
+  benchmark's data set) are committed as fixture data, the other nine xz-compressed: each is checked against the sha256
+  recorded when the fixture was made and re-counted by the product's StereoDataset."""
   import hashlib
   import json
+  import lzma
   rec = json.load(open(os.path.join(PIN, "split_lengths.json")))
   rows = {(r["split"], r["subsplit"]): r for r in rec["rows"]}
   assert {k: r["expected_by_reference_test"] for k, r in rows.items()} == {
@@ -169,8 +170,12 @@ def test_split_lengths_asserted_by_the_reference_test():
     assert hashlib.sha256(open(path, "rb").read()).hexdigest() == rows[("kitti_stereo_2015", sub)]["sha256"]
     first = d._paths(0)
     assert len(first) == 4 and first[0].endswith("image_2/000000_10.png") and first[1].endswith("image_3/000000_10.png")
-  ref_splits = "/root/reference/splits"
-  if os.path.isdir(ref_splits):
-    for (split, sub), r in rows.items():
-      d = StereoDataset("/nonexistent", r["dataset"], split, 320, 960, sub, scales=[0], splits_path=ref_splits)
-      assert len(d) == r["expected_by_reference_test"], (split, sub, len(d))
+  for (split, sub), r in rows.items():
+    if split == "kitti_stereo_2015":
+      continue
+    raw = lzma.decompress(open(os.path.join(PIN, "splits_xz", split, "%s_lines.txt.xz" % sub), "rb").read())
+    assert hashlib.sha256(raw).hexdigest() == r["sha256"], (split, sub)
+    os.makedirs(str(tmp_path / split), exist_ok=True)
+    (tmp_path / split / ("%s_lines.txt" % sub)).write_bytes(raw)
+    d = StereoDataset("/nonexistent", r["dataset"], split, 320, 960, sub, scales=[0], splits_path=str(tmp_path))
+    assert len(d) == r["expected_by_reference_test"], (split, sub, len(d))

@@ -16,8 +16,6 @@
 #include "photometric_dev.h"
 #pragma clang fp contract(off)
 
-#define PH_BLOCKS_PER_IMAGE 512     // x B workgroups: eight per CU at 4 images
-
 // ---- deterministic per-image reductions --------------------------------------------------
 // partial[b][blk] (fp64) then a fixed-order finalize.
 __global__ __launch_bounds__(256) void image_sum_kernel(const float* __restrict__ v, long n_per_image,

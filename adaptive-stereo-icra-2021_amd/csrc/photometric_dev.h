@@ -6,6 +6,10 @@
 #pragma once
 #include "as_common.h"
 
+// Workgroups per image of the per-image mean reduction (photometric.hip): its fp64 partials are B x this, and the workspaces of
+// both generations (photometric.hip, photometric_rows.hip) are sized from this one definition.
+#define PH_BLOCKS_PER_IMAGE 512     // x B workgroups: eight per CU at 4 images
+
 // ---- division by 9 and by 3 ---------------------------------------------------------------------
 // The kernels divide ~19 times per pixel by these two constants (the reference's avg_pool2d and means divide, so must we,
 // bit for bit) and an IEEE fp32 division is ~12 instructions.  q = x*c, r = fma(-q, y, x), q' = fma(r, c, q) with

@@ -507,7 +507,6 @@ struct RowsWs { float* mean; float* sum; double* partial; float* plane; };
 // the one-thread-per-pixel generation's per-image mean (photometric.hip)
 int as_photometric_image_mean(const float* pred, int B, long plane, double* partial, float* mean, hipStream_t st);
 
-#define ROWS_MEAN_BLOCKS 512
 // floats: [mean B | sum B, padded to 16 each] + fp64 partials (max of: the mean's B x 512, the forward's 2 x units, the
 // backward's units) + one [B][H][W] plane
 extern "C" int64_t as_photometric_chain_workspace(int B, int H, int W) {
@@ -515,7 +514,7 @@ extern "C" int64_t as_photometric_chain_workspace(int B, int H, int W) {
   const int64_t Bp = (B + 15) / 16 * 16;
   const int64_t max_units = (int64_t)B * ((H + 7) / 8) * ((W + 59) / 60);
   int64_t dbl = 2 * max_units;
-  if (dbl < (int64_t)B * ROWS_MEAN_BLOCKS) dbl = (int64_t)B * ROWS_MEAN_BLOCKS;
+  if (dbl < (int64_t)B * PH_BLOCKS_PER_IMAGE) dbl = (int64_t)B * PH_BLOCKS_PER_IMAGE;
   return 2 * Bp + 2 * dbl + (int64_t)B * H * W + 16;
 }
 
@@ -524,7 +523,7 @@ static RowsWs rows_carve(float* ws, int B, int H, int W) {
   const int64_t Bp = (B + 15) / 16 * 16;
   const int64_t max_units = (int64_t)B * ((H + 7) / 8) * ((W + 59) / 60);
   int64_t dbl = 2 * max_units;
-  if (dbl < (int64_t)B * ROWS_MEAN_BLOCKS) dbl = (int64_t)B * ROWS_MEAN_BLOCKS;
+  if (dbl < (int64_t)B * PH_BLOCKS_PER_IMAGE) dbl = (int64_t)B * PH_BLOCKS_PER_IMAGE;
   w.mean = ws; w.sum = ws + Bp;
   w.partial = reinterpret_cast<double*>(ws + 2 * Bp);
   w.plane = ws + 2 * Bp + 2 * dbl;

@@ -100,3 +100,17 @@ __device__ inline double wave_sum_d(double v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+
+// ---- shared by the three fp64 BatchNorm merges (bn_act.hip's finalize, bn_merge.h, trunk.hip) ---------------------------
+// The pivot of the one-pass merge is the mean of the first partial with a count above 0: an empty partial 0 (mean 0) as the
+// pivot would make the cancellation in S2 - S1^2/S0 grow with (mean/std)^2.  The merges sum with partial 0's mean as before,
+// their loads not waiting for any test; only when cnt[0] (the same for every lane, loaded beside them) turns out to be 0 do
+// they take this pivot and sum again.
+__device__ inline double bn_merge_pivot_scan(const float* stat_mean, const float* stat_cnt, int nparts, int c) {
+  for (int i = 1; i < nparts; ++i)
+    if (stat_cnt[i] > 0.f) return (double)stat_mean[i * 32 + c];
+  return (double)stat_mean[c];
+}
+// M2 = S2 - S1^2/S0 clamped at 0 against round-off, but a NaN stays NaN (non-finite data must not become variance 0);
+// every other value gives fmax's bits.
+__device__ inline double bn_clamp_m2(double d) { return d != d ? d : fmax(d, 0.0); }

@@ -92,25 +92,31 @@ __device__ inline void trunk_bn_merge(const TrunkBnIn& m, int group, double* red
   const float* s2 = m.stat_m2 + (long)group * m.nparts * 32;
   const float* sc = m.stat_cnt + (long)group * m.nparts;
   const int per_slice = (m.nparts + 7) >> 3;
-  const double K = (double)sm[c];
-  double s0 = 0.0, s1 = 0.0, sq = 0.0;
+  const float cnt0 = sc[0];
+  double K = (double)sm[c];
+  double s0, s1, sq;
   constexpr int BATCH = 12;                              // partials per thread whose loads are in flight together (96 per group per round)
-  for (int j0 = 0; j0 < per_slice; j0 += BATCH) {
-    float pn[BATCH], pm[BATCH], pq[BATCH];
+  for (int pass = 0; pass < 2; ++pass) {
+    s0 = 0.0; s1 = 0.0; sq = 0.0;
+    for (int j0 = 0; j0 < per_slice; j0 += BATCH) {
+      float pn[BATCH], pm[BATCH], pq[BATCH];
 #pragma unroll
-    for (int j = 0; j < BATCH; ++j) {
-      const int i = slc + 8 * (j0 + j);
-      const bool ok = i < m.nparts;
-      const int ii = ok ? i : 0;
-      pn[j] = ok ? sc[ii] : 0.f;
-      pm[j] = sm[ii * 32 + c];
-      pq[j] = ok ? s2[ii * 32 + c] : 0.f;
-    }
+      for (int j = 0; j < BATCH; ++j) {
+        const int i = slc + 8 * (j0 + j);
+        const bool ok = i < m.nparts;
+        const int ii = ok ? i : 0;
+        pn[j] = ok ? sc[ii] : 0.f;
+        pm[j] = sm[ii * 32 + c];
+        pq[j] = ok ? s2[ii * 32 + c] : 0.f;
+      }
 #pragma unroll
-    for (int j = 0; j < BATCH; ++j) {
-      const double n = (double)pn[j], dm = (double)pm[j] - K;
-      s0 += n; s1 += n * dm; sq += (double)pq[j] + n * dm * dm;
+      for (int j = 0; j < BATCH; ++j) {
+        const double n = (double)pn[j], dm = (double)pm[j] - K;
+        s0 += n; s1 += n * dm; sq += (double)pq[j] + n * dm * dm;
+      }
     }
+    if (cnt0 > 0.f || pass == 1) break;
+    K = bn_merge_pivot_scan(sm, sc, m.nparts, c);          // partial 0 empty: again, about a non-empty partial's mean
   }
   double* mine = red + (slc * 32 + c) * 3;
   mine[0] = s0; mine[1] = s1; mine[2] = sq;
@@ -120,7 +126,7 @@ __device__ inline void trunk_bn_merge(const TrunkBnIn& m, int group, double* red
     for (int j = 0; j < 8; ++j) { const double* r = red + (j * 32 + c) * 3; t0 += r[0]; t1 += r[1]; t2 += r[2]; }
     const double count = t0;
     const double mean = K + t1 / count;
-    const double m2 = fmax(t2 - t1 * t1 / count, 0.0);
+    const double m2 = bn_clamp_m2(t2 - t1 * t1 / count);
     const double var_b = m2 / count;
     const float invstd = (float)(1.0 / sqrt(var_b + (double)m.eps));
     const float meanf = (float)mean;

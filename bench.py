@@ -5,14 +5,18 @@ maxdisp 192 (k=4, input_scale=0), forward + one online-adaptation step, syntheti
 
   python bench.py --gpus 1 --steps 20 --warmup 5
   python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR    (+ the last timed step's results as DIR/*.npy)
+  python bench.py --gpus 1 --steps 20 --warmup 5 --full                (+ every other measurement, below)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
       --master-port P bench.py --gpus N --steps K --warmup W
 
 A "step" = feature nets on both images + StereoNet forward + LinearWarping + monodepth loss +
 FCS + backward + clip_grad_norm_(stereo_net, 1.0) + Adam(lr 5e-5) on a batch of `--batch` pairs
 per GPU (reference: adapt.py:304-396 NONSTOP / evaluation/stereonet_timing.py:44-72).
-Prints ONE JSON line (rank 0).  `value` is the adaptation-step rate; the forward-only rate
-(eval, no_grad, evaluation/stereonet_timing.py:22-41) is reported next to it.
+Prints ONE JSON line (rank 0).  `value` is the adaptation-step rate.  A plain run sets up, warms
+up, times the steps, dumps them if asked and prints that line.  With --full the line also carries
+the forward-only rate (eval, no_grad, evaluation/stereonet_timing.py:22-41), the per-kernel
+roofline and the side legs (sustained, batch16, sceneflow_fwd, online_batch1, dp_path_overhead_ms,
+cpu_baseline), each measured after the headline's timed steps.
 """
 import argparse
 import ctypes
@@ -62,6 +66,9 @@ def parse():
   ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed "
                   "adaptation step returned (loss, FCS, its EMA, every output map and the coarse arg-max) as DIR/<name>.npy "
                   "(rank 0; float32, float64 kept; at most 64 MB in all, a larger map is a fixed, seeded sample of its elements)")
+  ap.add_argument("--full", action="store_true", help="measure everything besides the headline, after its timed steps: the "
+                  "forward-only rate, the per-kernel roofline (the K steps once more, eagerly, with HIP events armed) and the "
+                  "side legs that the --no-* options above skip one by one; without it a run prints the headline alone")
   args = ap.parse_args()
   if args.steps < 1:
     ap.error("--steps must be at least 1")
@@ -435,21 +442,64 @@ def main():
   # Roofline leg: per-launch durations of the dominant kernels from HIP events on the launch stream.
   # Events cannot bracket nodes inside a graph replay, so with --graph the same K steps are run once
   # more eagerly, right after the timed region, with the events armed (same kernels, same shapes).
+  # With eager launches the headline is the better of the two regions, so a plain run keeps this one then.
   n_graphs = adapter.graph_count()
-  if use_graph:
-    adapter._graph = None
-  lib.as_prof_reset(); lib.as_prof_enable(1)
-  t_adapt_eager = timed(lambda: adapter.step(left, right), args.steps, world)
-  lib.as_prof_enable(0)
-  if not use_graph:
-    t_adapt = min(t_adapt, t_adapt_eager)
+  if args.full or not use_graph:
+    if use_graph:
+      adapter._graph = None
+    lib.as_prof_reset(); lib.as_prof_enable(1)
+    t_adapt_eager = timed(lambda: adapter.step(left, right), args.steps, world)
+    lib.as_prof_enable(0)
+    if not use_graph:
+      t_adapt = min(t_adapt, t_adapt_eager)
+
+  log("timed adapt: %.2f ms/step" % (1e3 * t_adapt / args.steps))
+  pairs = world * B * args.steps
+  out = {
+    "metric": "stereo pairs/sec (fwd+adapt-step), KITTI 1242x375 D=192",
+    "value": round(pairs / t_adapt, 3),
+    "unit": "stereo pairs/s",
+    "n_gpus": world,
+    "steps": args.steps,
+    "warmup": args.warmup,
+    "ms_per_step": round(1e3 * t_adapt / args.steps, 3),
+    "higher_is_better": True,
+    "scaling": "weak",
+    "vs_baseline": None,
+    "dtype": "f32",
+    "data": "synthetic",
+    "config": {"workload": "KITTI-2015 %dx%d, maxdisp %d, k=%d (Dc=%d, %dx%d cost volume), forward + one online-adapt "
+                           "step (train-mode BN, monodepth loss, clip 1.0, Adam lr 5e-5)" % (
+                               args.width, args.height, args.maxdisp, args.k, (args.maxdisp + 1) // 2 ** args.k,
+                               -(-args.height // 2 ** args.k), -(-args.width // 2 ** args.k)),
+               "pairs_per_gpu": B, "global_batch": world * B,
+               "parallelism": "dp%d (%s BatchNorm statistics, one flat RCCL gradient all-reduce)" % (
+                   world, "cross-replica" if adapter.bn_sync is not None else "per-replica"),
+               "kernels": "all hand-written HIP (no MIOpen/rocBLAS on the path)"},
+    "launch_mode": ("hipGraph replay of the captured step (%d graph%s)" % (n_graphs, "" if n_graphs == 1 else "s"))
+                   if use_graph else "eager",
+    "collectives": None if world == 1 else (
+        ("RCCL through the library's own communicator" if adapter.comm is not None else "torch.distributed") +
+        (", eager" if not use_graph else (", captured in the step's graph" if adapter.comm is not None else ", between two graphs"))),
+  }
+  if world > 1 and adapter.comm is not None:
+    # what the communicator's first collectives returned (adaptive_stereo/rccl.py, stage "probe"): an all-reduce of ones = the
+    # number of ranks that took part, an all-gather of each rank's HIP device, the library's version
+    out["rccl"] = getattr(adapter.comm, "evidence", None)
+  if not args.full:
+    if rank == 0:
+      emit_json(out)
+    if world > 1:
+      adapter.close()
+      dist.destroy_process_group()
+    return
+
+  # ---- --full: what the profiled region above recorded, the forward-only rate, the roofline, the side legs ------------------
   prof = []
   for kid in range(28):             # AS_PROF_IDS (csrc/as_common.h)
     n, ms, fl = ctypes.c_int64(0), ctypes.c_double(0), ctypes.c_double(0)
     nat.call("as_prof_read", kid, ctypes.byref(n), ctypes.byref(ms), ctypes.byref(fl))
     prof.append((n.value, ms.value, fl.value))
-
-  log("timed adapt: %.2f ms/step" % (1e3 * t_adapt / args.steps))
   # ---- forward only --------------------------------------------------------------------------
   for _ in range(max(1, args.warmup // 2)):
     adapter.infer(left, right)
@@ -475,7 +525,6 @@ def main():
       dist.destroy_process_group()
     return
 
-  pairs = world * B * args.steps
   # Per-kernel entries: algorithmic FLOPs per launch (direct form: 2 * voxels * 32 * 32 * taps) / mean launch duration from
   # HIP events recorded on the launch stream.  Which kernel is the dominant one is decided below, by time per step.
   def entry(i, name):
@@ -673,41 +722,12 @@ def main():
     roofline["whole_forward"] = {"flops_per_pair": mf["forward"], "achieved": round(fwd_tf / world, 2), "unit": "TFLOP/s per GPU",
                                  "frac": round(fwd_tf / world / FP32_MFMA_PEAK_TFLOPS, 4),
                                  "breakdown_gflop_per_pair": {k_: round(v / 1e9, 3) for k_, v in mf.items()}}
-  out = {
-    "metric": "stereo pairs/sec (fwd+adapt-step), KITTI 1242x375 D=192",
-    "value": round(pairs / t_adapt, 3),
-    "unit": "stereo pairs/s",
-    "n_gpus": world,
-    "steps": args.steps,
-    "warmup": args.warmup,
-    "ms_per_step": round(1e3 * t_adapt / args.steps, 3),
-    "higher_is_better": True,
-    "scaling": "weak",
-    "vs_baseline": None,
-    "dtype": "f32",
-    "data": "synthetic",
-    "config": {"workload": "KITTI-2015 %dx%d, maxdisp %d, k=%d (Dc=%d, %dx%d cost volume), forward + one online-adapt "
-                           "step (train-mode BN, monodepth loss, clip 1.0, Adam lr 5e-5)" % (
-                               args.width, args.height, args.maxdisp, args.k, (args.maxdisp + 1) // 2 ** args.k,
-                               -(-args.height // 2 ** args.k), -(-args.width // 2 ** args.k)),
-               "pairs_per_gpu": B, "global_batch": world * B,
-               "parallelism": "dp%d (%s BatchNorm statistics, one flat RCCL gradient all-reduce)" % (
-                   world, "cross-replica" if adapter.bn_sync is not None else "per-replica"),
-               "kernels": "all hand-written HIP (no MIOpen/rocBLAS on the path)"},
-    "launch_mode": ("hipGraph replay of the captured step (%d graph%s)" % (n_graphs, "" if n_graphs == 1 else "s"))
-                   if use_graph else "eager",
-    "collectives": None if world == 1 else (
-        ("RCCL through the library's own communicator" if adapter.comm is not None else "torch.distributed") +
-        (", eager" if not use_graph else (", captured in the step's graph" if adapter.comm is not None else ", between two graphs"))),
+  out.update({
     "eager_ms_per_step": round(1e3 * t_adapt_eager / args.steps, 3),
     "fwd_pairs_per_s": round(pairs / t_fwd, 3),
     "fwd_ms_per_step": round(1e3 * t_fwd / args.steps, 3),
     "roofline": roofline,
-  }
-  if world > 1 and adapter.comm is not None:
-    # what the communicator's first collectives returned (adaptive_stereo/rccl.py, stage "probe"): an all-reduce of ones = the
-    # number of ranks that took part, an all-gather of each rank's HIP device, the library's version
-    out["rccl"] = getattr(adapter.comm, "evidence", None)
+  })
   if world == 1 and use_graph and not args.no_legs:
     # "sustained": the captured step replayed back to back for >= 2 s (the 20-step region above lasts ~0.15 s)
     adapter.capture(left, right, warmup=1)

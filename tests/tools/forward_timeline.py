@@ -1,4 +1,4 @@
-"""Lists the kernels of the LAST forward-only (inference) step of a rocprofv3 --kernel-trace of bench.py with their
+"""Lists the kernels of the LAST forward-only (inference) step of a rocprofv3 --kernel-trace of bench.py --full with their
 start offsets, so that overlap between the two feature-extraction streams is visible.
 usage: python tests/tools/forward_timeline.py <kernel_trace.csv>"""
 import csv, sys

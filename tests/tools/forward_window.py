@@ -1,4 +1,4 @@
-"""Summarises the forward-only (inference) steps at the end of a rocprofv3 --kernel-trace of bench.py.
+"""Summarises the forward-only (inference) steps at the end of a rocprofv3 --kernel-trace of bench.py --full.
 usage: python tests/tools/forward_window.py <kernel_trace.csv> <timed_steps>"""
 import collections, csv, sys
 path, steps = sys.argv[1], int(sys.argv[2])

@@ -25,7 +25,7 @@ for k, d in acc.items():
          "wave_residency_of_kernel": round(4 * m.get("SQ_WAVE_CYCLES", 0) / max(m.get("SQ_WAVES", 1), 1) / cyc, 4) if cyc else None,
          "raw": {c: round(v, 1) for c, v in m.items()}}
   res[k[:110]] = rec
-json.dump({"pairs_per_step": pairs, "command": "rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE -- python3 bench.py --steps 3 --warmup 2 --no-cpu-baseline --no-graph --one-stream --batch %d" % pairs,
+json.dump({"pairs_per_step": pairs, "command": "rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE -- python3 bench.py --steps 3 --warmup 2 --full --no-cpu-baseline --no-graph --one-stream --batch %d" % pairs,
            "kernels": dict(sorted(res.items(), key=lambda kv: -kv[1]["kernel_cycles"] * kv[1]["dispatches"]))}, open(out, "w"), indent=1)
 for k, v in list(json.load(open(out))["kernels"].items())[:40]:
   print("%-70s n=%4d cyc %8.0f waves %6.0f mfma %.3f wait %.2f inst-wait %.2f active %.2f resid %.2f" % (k[:70], v["dispatches"], v["kernel_cycles"], v["waves"] or 0, v["mfma_busy_fraction_of_simd_cycles"] or 0, v["wait_any_share"], v["wait_inst_share"], v["active_inst_share"], v["wave_residency_of_kernel"] or 0))

@@ -5,6 +5,11 @@
 // tensors x ~6 ops).  Here parameters, gradients and both moments live at equal offsets
 // of flat arenas (the same flat gradient arena is the RCCL all-reduce bucket), so the whole
 // update is one sum-of-squares reduction and one element-wise pass.  HBM-bound, 1.7 MB.
+// Documented deviation from torch: the ABI takes lr, beta1, beta2 and eps as float, so the kernel forms 1.f - b2 from 0.999f
+// where torch forms 1 - 0.999 in double.  The weight of g*g in exp_avg_sq therefore differs from torch's by
+// |(1 - float(b2)) - (1 - b2)| / (1 - b2) = 1.29e-5 relative for 0.999, the update by at most half of that (the bias correction
+// is built from the same rounded b2) plus the float roundings of lr and beta1, 7.0e-6 in all.  tests/adam_ref.py has both
+// forms, tests/test_adam_ref_cpu.py pins their distance, tests/test_gpu_optim_fp64.py holds the kernel to the float form.
 #include "as_common.h"
 #include <string.h>
 
@@ -186,6 +191,12 @@ extern "C" int as_sumsq_clip(const float* g, int64_t n, float max_norm, float* o
 
 // torch.optim.Adam (single-tensor path): m = lerp(m, g, 1-b1); v = b2*v + (1-b2)*g*g;
 // denom = sqrt(v)/sqrt(bc2) + eps; p -= (lr/bc1) * m / denom.
+// The clipped gradient is ONE float32 product, as clip_grad_norm_ stores it: contracted into "g * gs - m" it reached exp_avg
+// unrounded while exp_avg_sq squared the rounded value, and no single Adam step describes both moments to 3 * 2^-24.
+__device__ inline float clipped_grad(float g, float gs) {
+#pragma clang fp contract(off)
+  return g * gs;
+}
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                     float* __restrict__ m, float* __restrict__ v, long n,
                                                     const float* __restrict__ grad_scale, float lr, float b1, float b2,
@@ -197,7 +208,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
   const float gs = grad_scale ? grad_scale[0] : 1.f;
   const float step_size = lr / bc1;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-    const float gi = g[i] * gs;
+    const float gi = clipped_grad(g[i], gs);
     const float mi = m[i] + (1.f - b1) * (gi - m[i]);
     const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
     m[i] = mi; v[i] = vi;

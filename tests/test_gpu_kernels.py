@@ -311,6 +311,8 @@ def test_softargmax_ties_and_extremes():
 # ----------------------------------------------------------------------------- a6
 @pytest.mark.parametrize("B,h,w,H,W", [(1, 3, 4, 24, 32), (2, 24, 78, 375, 1242), (1, 10, 17, 75, 131), (1, 1, 1, 5, 7)])
 def test_upsample_bilinear(B, h, w, H, W):
+  """Smoke-level parity with ATen in float32 through the autograd function.  The bounds that pin the kernels (float64 reference,
+  per-element bound from the kernel's own arithmetic, guard words, every launch path) are in tests/test_gpu_resample_fp64.py."""
   src = rnd(B, h, w, seed=1).requires_grad_(True)
   gain = W / w
   ref = F.interpolate(src.unsqueeze(1), size=(H, W), mode="bilinear", align_corners=False) * gain
@@ -413,6 +415,8 @@ def test_masked_mean_matches_boolean_index_mean():
 
 # ----------------------------------------------------------------------------- a12
 def test_sumsq_and_adam_step():
+  """Three steps against the float32 oracle, end to end.  The one-step float64 bounds on exp_avg, exp_avg_sq and the update, the
+  device step counter, the clip coefficient and graph replay are in tests/test_gpu_optim_fp64.py."""
   n = 313698
   p, g = rnd(n, seed=1), rnd(n, seed=2, scale=1e-2)
   lib = nat.load()

@@ -52,6 +52,11 @@ class TrunkBn(ctypes.Structure):
              [("nparts", ctypes.c_int32), ("eps", c_float)]
 
 
+class DepthCamera(ctypes.Structure):
+  """as_depth_camera: fp32 camera constants at one pyramid level + the depth image's clamp, scale and truncation."""
+  _fields_ = [(n, c_float) for n in ("fb", "fxs", "fys", "cxs", "cys", "max_depth", "depth_scale", "depth_trunc")]
+
+
 _P = ctypes.POINTER
 _SIGNATURES = {
   # name: (restype, [argtypes])
@@ -205,6 +210,11 @@ _SIGNATURES = {
   "as_decode_rgb8": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp]),
   "as_decode_plane": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_vp,
                               c_vp]),
+  "as_voxel_table_slots": (c_i64, [c_i64]),
+  "as_voxel_table_bytes": (c_i64, [c_int, c_i64]),
+  "as_voxel_table_clear": (c_int, [c_vp, c_int, c_i64, c_vp]),
+  "as_disp_to_points": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, _P(DepthCamera), c_vp, c_vp, c_float, c_vp, c_i64, c_vp]),
+  "as_voxel_cloud_finalize": (c_int, [c_vp, c_int, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
   "as_prof_enable": (c_int, [c_int]),
   "as_prof_reset": (c_int, []),
   "as_prof_read": (c_int, [c_int, _P(c_i64), _P(ctypes.c_double), _P(ctypes.c_double)]),

@@ -659,6 +659,53 @@ int as_decode_rgb8(const uint8_t* src, int H0, int W0, int i0, int j0, int H, in
 int as_decode_plane(const void* src, int dtype, int H0, int W0, int i0, int j0, int H, int W, int hflip,
                     int vflip, float scale, int reciprocal, float* dst, void* stream);
 
+/* ---- depth and point cloud from disparity (csrc/pointcloud.hip) — ros/stereo_depth_node.py:145-195 ----------
+ * What the reference's ROS node computes on the host (F.interpolate to pyramid level s, depth = fx*b/disp, clamp,
+ * Open3D's 16-bit depth image, pinhole back-projection, voxel_down_sample, the x,y,z,rgb records of
+ * ros/open3d_to_ros.py:15-22,57).  disp [B,1,H,W] is full-resolution disparity in pixels, rgb [B,3,H,W] in [0,1]
+ * (may be NULL); n = 2^s, h = H >> s, w = W >> s (trailing rows and columns of a ragged size are unused).
+ * Every fp32 expression is a sequence of single IEEE operations in the written order (no fma):
+ *   m      = ((a + b) + (c + d)) * 0.25f over source pixels (n*v+o, n*u+o), (.., +1), (+1, ..), (+1, +1), o = n/2 - 1;
+ *            m = disp[v,u] for s = 0.  Colour: the same pixels and formula per channel.
+ *   depth  = fminf(fb / m, max_depth), negative -> 0, NaN stays NaN (the pixel is invalid)
+ *   q      = (int)(depth * depth_scale), z = (float)q / depth_scale; invalid when q == 0 or z > depth_trunc.
+ *            depth_scale == 0: z = depth, invalid unless 0 < z <= depth_trunc.
+ *   x      = (((float)u - cxs) * z) / fxs,  y = (((float)v - cys) * z) / fys
+ *   voxel  ix = (int)floorf(x / voxel_size) (iy, iz likewise), anchored at the camera origin; a point with an |i| >= 2^20
+ *            is counted in dropped[b] and not inserted.  Per voxel, all integers: count, Sx/Sy/Sz += llrintf(coord *
+ *            65536.f) (64 bit), Sr/Sg/Sb += (int)(colour * 255.f) clamped to 0..255.
+ *   record X = (float)((double)Sx / ((double)count * 65536.0)) (Y, Z likewise), R = Sr / count: 16 bytes x, y, z fp32 and
+ *            a u32 R << 16 | G << 8 | B (0 without colour).  Integer sums: a voxel's record does not depend on arrival order.
+ * The camera holds fp32 values rounded once on the host from full-resolution intrinsics: fb = fx * baseline, fxs = fx / n,
+ * fys, cxs, cys likewise.  max_depth * depth_scale <= 65535.
+ *
+ * as_voxel_table_slots: default slot count for that many points per image: a power of two >= 2 * points, >= 1024.
+ * as_voxel_table_bytes: size of the table workspace (16-byte aligned) for B images of `slots` slots.
+ * as_voxel_table_clear: empties a table.  ONCE after allocation: as_voxel_cloud_finalize hands every slot it read back
+ *   empty, so call-to-call independence costs no pass over the table; a frame never sees an earlier frame's voxels as long
+ *   as every as_disp_to_points with a table is followed by its finalize (clear again after abandoning a frame in between).
+ * as_disp_to_points: one pass over the frame.  depth_out [B,1,h,w] (the clamped depth, before quantisation), xyz_out
+ *   [B,3,h,w] (x, y, z planes, NaN at invalid pixels) and table may each be NULL.  With a table every valid point is
+ *   inserted into its image's open-addressing hash table (64-bit key of three biased 21-bit indices, atomicCAS on the key,
+ *   linear probing bounded by `slots` probes — a point that finds no slot is counted in dropped[b] — then integer
+ *   atomicAdds).  slots: a power of two >= max(64, h*w); voxel_size in (0, 16]; B <= 65535.
+ * as_voxel_cloud_finalize: compacts the occupied slots of image b into rows [0, n[b]) of records [B][cap] (16 bytes each,
+ *   16-byte aligned), voxel [B][cap][3], count [B][cap]; n [B] and dropped [B] are overwritten.  Rows at or beyond n[b]
+ *   are left untouched, the order of rows within an image is unspecified; voxels beyond cap are counted in n[b] but not
+ *   written (cap = h*w always suffices). */
+typedef struct as_depth_camera {
+  float fb;                       /* float32(fx * baseline) */
+  float fxs, fys, cxs, cys;       /* float32(fx / n) ... at pyramid level s */
+  float max_depth, depth_scale, depth_trunc;
+} as_depth_camera;
+int64_t as_voxel_table_slots(int64_t points_per_image);
+int64_t as_voxel_table_bytes(int B, int64_t slots);
+int as_voxel_table_clear(void* table, int B, int64_t slots, void* stream);
+int as_disp_to_points(const float* disp, const float* rgb, int B, int H, int W, int s, const as_depth_camera* cam,
+                      float* depth_out, float* xyz_out, float voxel_size, void* table, int64_t slots, void* stream);
+int as_voxel_cloud_finalize(void* table, int B, int64_t slots, int cap, void* records, int32_t* voxel, int32_t* count,
+                            int32_t* n, int32_t* dropped, void* stream);
+
 /* ---- measurement hook (bench.py roofline leg) -----------------------------------
  * When enabled, as_conv32_fwd and as_conv32_wgrad bracket their main kernel with HIP events on the
  * launch stream and account its algorithmic FLOPs (2 * voxels * 32 * 32 * taps).  Kernel ids:

@@ -6,6 +6,9 @@ soft-argmax kernel already produces in the same pass over the logits.  StereoNet
 that by-product to the logits tensor together with the tensor's version counter; a volume that did not
 come from StereoNet — or one a caller has edited in place since (the counter moved) — is scored by running
 the kernel on it, as the reference recomputes on every call.
+
+feature_contrast_median (reference :4-9, ``max - torch.median`` along Dc: the lower median) has no by-product to reuse: it is
+one launch of as_fcs_scores (csrc/ood.hip) with only the median map requested.
 """
 import torch
 
@@ -23,4 +26,15 @@ def feature_contrast_mean(cost_volume):
     pred = torch.empty(B, H, W, dtype=torch.float32, device=logits.device)
     fcs = torch.empty_like(pred)
     nat.call("as_softargmax_fwd", nat.ptr(logits), B, D, H, W, nat.ptr(pred), None, nat.ptr(fcs), nat.stream())
+    return fcs
+
+
+def feature_contrast_median(cost_volume):
+  nat.require_gpu(cost_volume)
+  with torch.no_grad():
+    logits = nat.f32c(cost_volume.detach())
+    B, D, H, W = logits.shape
+    fcs = torch.empty(B, H, W, dtype=torch.float32, device=logits.device)
+    with torch.cuda.device(logits.device):
+      nat.call("as_fcs_scores", nat.ptr(logits), B, D, H, W, None, nat.ptr(fcs), None, 0, None, None, nat.stream())
     return fcs

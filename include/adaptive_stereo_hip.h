@@ -706,6 +706,28 @@ int as_disp_to_points(const float* disp, const float* rgb, int B, int H, int W, 
 int as_voxel_cloud_finalize(void* table, int B, int64_t slots, int cap, void* records, int32_t* voxel, int32_t* count,
                             int32_t* n, int32_t* dropped, void* stream);
 
+/* ---- per-image feature-contrast scores (csrc/ood.hip) — evaluation/ood_analysis.py:76-77, utils/feature_contrast.py ------
+ * One pass over logits [B][D][H][W] (dense fp32, as as_softargmax_fwd reads it), 1 <= D <= 64 (more: AS_ERR_ARG before any
+ * launch), B <= 65535.  Outputs, each may be NULL (at least one is not):
+ *   fcs_mean [B][H][W]    m1 - (sum - m1 - m2) / (float)(D - 2) for D > 2, else 0: sum = fp32 sum of the D values in increasing
+ *                         d starting from 0.f; m1, m2 = the largest and second largest (`if (v > m1) { m2 = m1; m1 = v; } else
+ *                         if (v > m2) m2 = v;` from -inf, -inf).  Expression for expression the fcs of as_softargmax_fwd: the
+ *                         same bits for finite logits.
+ *   fcs_median [B][H][W]  m1 - e, e = the element of rank (D - 1) / 2 (integer division) when the D values are put in ascending
+ *                         order, equal values in order of d: torch.median's lower median.  One fp32 subtraction of two inputs.
+ *   A pixel with a NaN among its D values is NaN (0x7FC00000) in both maps, for every D.
+ *   scores                row r = (cursor ? *cursor : 0) + b holds, when 0 <= r < capacity, two floats at scores + 2 * r:
+ *                         (float)(S / (double)(H * W)) with S the fp64 sum of the image's mean map, then the same of its median
+ *                         map.  S is summed in a fixed order (lane t of 512: pixels t, t + 512, ... in order; xor butterfly over
+ *                         the 64 lanes of a wave, offsets 32 down to 1; the 8 waves in order): no atomics, no workspace, the same
+ *                         bits on every run.  Rows outside [0, capacity) are not written.
+ *   cursor, dropped       device int32, each may be NULL, both NULL without scores.  After the rows are written, in stream order
+ *                         (a second, one-lane launch): *dropped += the number of rows of this call that were not written;
+ *                         *cursor += B (saturating at INT32_MAX - 65535; a negative cursor is left alone).  A captured graph
+ *                         that contains the call appends on every replay. */
+int as_fcs_scores(const float* logits, int B, int D, int H, int W, float* fcs_mean, float* fcs_median, float* scores,
+                  int capacity, int32_t* cursor, int32_t* dropped, void* stream);
+
 /* ---- measurement hook (bench.py roofline leg) -----------------------------------
  * When enabled, as_conv32_fwd and as_conv32_wgrad bracket their main kernel with HIP events on the
  * launch stream and account its algorithmic FLOPs (2 * voxels * 32 * 32 * taps).  Kernel ids:

@@ -216,6 +216,11 @@ _SIGNATURES = {
   "as_disp_to_points": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, _P(DepthCamera), c_vp, c_vp, c_float, c_vp, c_i64, c_vp]),
   "as_voxel_cloud_finalize": (c_int, [c_vp, c_int, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
   "as_fcs_scores": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp]),
+  "as_lidar_zbuf_clear": (c_int, [c_vp, c_int, c_int, c_int, c_vp]),
+  "as_lidar_project": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp]),
+  "as_lidar_resolve_workspace": (c_i64, [c_int, c_int, c_int]),
+  "as_lidar_resolve": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.c_double, c_int, c_vp, c_vp, c_vp,
+                               c_vp, c_vp, c_vp, c_vp, c_vp]),
   "as_prof_enable": (c_int, [c_int]),
   "as_prof_reset": (c_int, []),
   "as_prof_read": (c_int, [c_int, _P(c_i64), _P(ctypes.c_double), _P(ctypes.c_double)]),

@@ -728,6 +728,53 @@ int as_voxel_cloud_finalize(void* table, int B, int64_t slots, int cap, void* re
 int as_fcs_scores(const float* logits, int B, int D, int H, int W, float* fcs_mean, float* fcs_median, float* scores,
                   int capacity, int32_t* cursor, int32_t* dropped, void* stream);
 
+/* ---- LiDAR ground truth: Velodyne scan -> sparse depth and disparity (csrc/lidar.hip) — scripts/export_gt_disp.py:86-115,156-162 ----
+ * What the reference's export script computes on the host per frame: the scan is projected into a rectified camera, the nearest
+ * return is kept per pixel, depth becomes disparity = baseline * fx / depth and is stored as uint16 = 128 * disp.
+ * points [B][Nmax][4] fp32 in KITTI .bin layout (x forward, y left, z up, reflectance; 16-byte aligned), counts [B] int32 ON THE
+ * DEVICE (a captured graph replays scans of different lengths; lanes at or beyond min(counts[b], Nmax) read nothing, 0 is legal),
+ * P [B][3][4] fp64 row-major (velodyne -> image: P_rect_0c . R_rect_00 (4x4) . [R|T], composed on the host), zbuf [B][H][W] uint32.
+ *
+ * as_lidar_project, per point, in fp64, every expression a sequence of single IEEE operations in the written order (no fma):
+ *   keep     x >= 0 (fp32 compare: keeps -0.0, drops NaN); the point is (x, y, z, 1), its fourth word is never used
+ *   q_k    = ((P[k][0] * x + P[k][1] * y) + P[k][2] * z) + P[k][3]            k = 0, 1, 2
+ *   u      = rint(q0 / q2) - 1.0, v = rint(q1 / q2) - 1.0     round half to even, as np.round; there is NO test of q2 > 0: a
+ *            point behind the camera that lands in bounds is kept, as in the reference
+ *   keep     0 <= u < W and 0 <= v < H, compared in fp64 (inf and NaN fail them as they do in numpy)
+ *   value  = x (the fp32 input) when vel_depth, else (float)q2 (round to nearest)
+ *   key    = the value's bits with the sign bit flipped when the value is positive, all bits flipped when it is negative: unsigned
+ *            order = float order (-0.0 just below +0.0), so a negative q2 wins the minimum and the pixel resolves to depth 0
+ *   zbuf[b][v][u] = min(zbuf[b][v][u], key) by atomicMin.  The empty key is 0xFFFFFFFF (no value encodes to it).  An integer
+ *            minimum does not depend on arrival order: the buffer is deterministic.
+ * The reference finds duplicates through a linear index row * (W - 1) + col - 1, which pixel (r, W-1) shares with pixel (r+1, 0);
+ * this keeps the minimum PER PIXEL, what the comment there says.  Only columns 0 and W-1 can differ from the reference.
+ *
+ * as_lidar_resolve, one pass over zbuf, per pixel of the window (i0, j0, h, w) inside H x W:
+ *   depth  = 0 for an empty key, else the decoded value, and 0 where that is < 0 (-0.0 stays -0.0, as in the reference)
+ *   disp64 = bf / (double)depth in fp64, bf = baseline * fx as fp64; 0 where depth == 0 or depth > 80 (fp32 compares).  The
+ *            reference divides an np.float64 scalar by a float32 array, which numpy >= 2 (checked with 2.2.6) promotes to float64,
+ *            so its division and its * 128.0 are fp64 as well.
+ *   q      = (uint16)trunc(128.0 * disp64).  Where 128.0 * disp64 > 65535 the reference asserts; here the pixel is 0 in EVERY
+ *            output (depth too) and is counted in overflow[b].
+ *   disp   = (float)q / 128.f when quantize (bit for bit what as_decode_plane yields from the exported file), else (float)disp64.
+ * Outputs, each may be NULL: depth_out [B][1][h][w] fp32, disp_out [B][1][h][w] fp32, disp_u16 [B][h][w], overflow [B] int32
+ * (overwritten; integer atomics).  pred [B][1][h][w] fp32 (may be NULL) comes with metrics [B][6] and workspace
+ * (as_lidar_resolve_workspace(B, H, W) BYTES, 8-byte aligned): row b of metrics has the layout of as_eval_metrics' out6 over the
+ * window's pixels with disp > 0 of image b, |pred - disp| and the strict > 2, 3, 4, 5 in fp32.  No float atomics: each
+ * workgroup of 256 consecutive pixels writes six fp64 partials (xor butterfly over the wave, offsets 32 down to 1, then the four
+ * waves in order); one wave per image adds them (lane t: blocks t, t + 64, ... in order, then the butterfly) and rounds to fp32
+ * once.  Counts are exact, a replay gives the same bits.
+ * The pass reads EVERY pixel of zbuf, outside the window too, and hands each key it read back empty: call-to-call independence
+ * costs no pass of its own.  as_lidar_zbuf_clear empties the buffer ONCE after allocation; clear again after abandoning a frame
+ * between its project and its resolve (the contract of the voxel table above).  B <= 65535, H * W < 2^30. */
+int as_lidar_zbuf_clear(uint32_t* zbuf, int B, int H, int W, void* stream);
+int as_lidar_project(const float* points, const int32_t* counts, const double* P, int B, int Nmax, int H, int W, int vel_depth,
+                     uint32_t* zbuf, void* stream);
+int64_t as_lidar_resolve_workspace(int B, int H, int W);
+int as_lidar_resolve(uint32_t* zbuf, int B, int H, int W, int i0, int j0, int h, int w, double bf, int quantize,
+                     float* depth_out, float* disp_out, uint16_t* disp_u16, const float* pred, float* metrics, void* workspace,
+                     int32_t* overflow, void* stream);
+
 /* ---- measurement hook (bench.py roofline leg) -----------------------------------
  * When enabled, as_conv32_fwd and as_conv32_wgrad bracket their main kernel with HIP events on the
  * launch stream and account its algorithmic FLOPs (2 * voxels * 32 * 32 * taps).  Kernel ids:

@@ -221,6 +221,11 @@ _SIGNATURES = {
   "as_lidar_resolve_workspace": (c_i64, [c_int, c_int, c_int]),
   "as_lidar_resolve": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.c_double, c_int, c_vp, c_vp, c_vp,
                                c_vp, c_vp, c_vp, c_vp, c_vp]),
+  "as_colormap_workspace": (c_i64, [c_int, c_i64]),
+  "as_colormap_range": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp]),
+  "as_colormap_apply": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_vp, c_vp, c_int, c_int, c_vp,
+                                c_vp]),
+  "as_image_to_cv": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_vp, c_vp]),
   "as_prof_enable": (c_int, [c_int]),
   "as_prof_reset": (c_int, []),
   "as_prof_read": (c_int, [c_int, _P(c_i64), _P(ctypes.c_double), _P(ctypes.c_double)]),

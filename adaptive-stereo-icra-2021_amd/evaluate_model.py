@@ -1,0 +1,143 @@
+"""The reference's evaluate_model.py with its flags, on this package: saved predictions, per-frame images, metrics.
+
+  --mode save      every "pred_disp" output of the network per sample as <weights>/outputs/<split>/<key with / as _>/<index>.pt
+                   (evaluate_model.py:16-20, 34-70)
+  --mode video     per frame left_#####.png, gt_#####.png (inferno, 0 .. 0.6 * 192) and pred_#####.png under the output folder's
+                   video/, written through PIL from images painted on the device; the per-frame EPE is printed and written to
+                   epe.csv.  The reference's text overlay needs OpenCV and is left out.
+  --mode playback  needs a display and OpenCV windows: raises.
+  --mode eval      does nothing in the reference; here it prints train.evaluate()'s metrics.
+
+Each mode is a function over a dataset-like iterable of {"color_l/0", "color_r/0", "gt_disp_l/0"} samples.
+"""
+import argparse
+import csv
+import os
+
+import torch
+from torch.utils.data import DataLoader
+
+import adaptive_stereo.utils.path_utils as paths
+from adaptive_stereo.utils.visualization import DisparityPainter
+from train import evaluate, process_batch
+
+VIDEO_CMAP, VIDEO_VMIN, VIDEO_VMAX = "inferno", 0, 0.6 * 192
+
+
+def get_save_filename(save_folder, outputs_key, index):
+  """<save_folder>/<key with / as _>/<index, four digits>.pt; the key's folder is created."""
+  folder = os.path.join(save_folder, "_".join(outputs_key.split("/")))
+  os.makedirs(folder, exist_ok=True)
+  return os.path.join(folder, "%04d.pt" % index)
+
+
+def save_outputs(feature_net, stereo_net, batches, save_folder, batch_size, opt=None):
+  """batches: an iterable of collated samples (a DataLoader, or a list of dicts of [b,...] tensors).  Returns the number of
+  samples written per key."""
+  feature_net.eval(); stereo_net.eval()
+  written = 0
+  with torch.no_grad():
+    for i, inputs in enumerate(batches):
+      left, right = inputs["color_l/0"].cuda(), inputs["color_r/0"].cuda()
+      outputs = process_batch(feature_net, stereo_net, left, right, opt, output_cost_volume=True)
+      for key in outputs:
+        if "pred_disp" in key:
+          for j in range(len(outputs[key])):
+            torch.save(outputs[key][j].detach().cpu().clone(), get_save_filename(save_folder, key, batch_size * i + j))
+      written += left.shape[0]
+      total = " of %d" % len(batches) if hasattr(batches, "__len__") else ""
+      print("saved batch %d%s (%d samples)" % (i + 1, total, written), flush=True)
+  return written
+
+
+def frame_epe(pred, gt):
+  """Mean |pred - gt| over gt > 0 of one frame (evaluate_model.py:110), a Python float."""
+  valid = gt > 0
+  return float((pred - gt).abs()[valid].mean())
+
+
+def write_video_frames(samples, save_folder, video_folder, frames=-1):
+  """samples: an iterable of single samples (tensors [C,H,W]); the predictions are the files save_outputs wrote.  Returns the
+  list of per-frame EPEs."""
+  from PIL import Image
+  os.makedirs(video_folder, exist_ok=True)
+  painter, epes = None, []
+  with open(os.path.join(video_folder, "epe.csv"), "w", newline="") as f:
+    rows = csv.writer(f)
+    rows.writerow(["frame", "epe"])
+    for i, inputs in enumerate(samples):
+      if frames > 0 and i >= frames:
+        break
+      left = inputs["color_l/0"].cuda().float().contiguous()
+      gt = inputs["gt_disp_l/0"].cuda().float().contiguous()
+      pred = torch.load(get_save_filename(save_folder, "pred_disp_l/0", i)).cuda().float().contiguous()
+      if painter is None:
+        painter = DisparityPainter(gt.shape[-2], gt.shape[-1], batch=1, cmap=VIDEO_CMAP, vmin=VIDEO_VMIN, vmax=VIDEO_VMAX,
+                                   order="rgb", out="u8", device=gt.device)          # PIL takes RGB
+      epe = frame_epe(pred, gt)
+      print("EPE:", epe)
+      rows.writerow([i, "{:.6f}".format(epe)])
+      epes.append(epe)
+      for name, image in (("left", painter.rgb(left)[0].cpu()), ("gt", painter.paint(gt)[0].cpu()),
+                          ("pred", painter.paint(pred)[0].cpu())):
+        Image.fromarray(image.numpy()).save(os.path.join(video_folder, "{}_{:05d}.png".format(name, i)))
+  return epes
+
+
+def load_networks(opt):
+  from adaptive_stereo.models.stereo_net import StereoNet, FeatureExtractorNetwork
+  feature_net = FeatureExtractorNetwork(opt.stereonet_k).cuda()
+  stereo_net = StereoNet(opt.stereonet_k, 1, 0).cuda()
+  feature_net.load_state_dict(torch.load(os.path.join(opt.load_weights_folder, "feature_net.pth"), map_location="cpu"), strict=True)
+  stereo_net.load_state_dict(torch.load(os.path.join(opt.load_weights_folder, "stereo_net.pth"), map_location="cpu"), strict=True)
+  return feature_net, stereo_net
+
+
+def main(opt):
+  if opt.mode == "playback":
+    raise RuntimeError("--mode playback opens OpenCV windows and needs a display; use --mode video and view the PNGs")
+  from adaptive_stereo.datasets.stereo_dataset import StereoDataset
+  save_folder = os.path.join(opt.load_weights_folder, "outputs", opt.split)
+  os.makedirs(save_folder, exist_ok=True)
+  dataset = StereoDataset(opt.dataset_path, opt.dataset_name, opt.split, opt.height, opt.width, opt.subsplit, scales=opt.scales,
+                          do_hflip=False, random_crop=False, load_disp_left=True, load_disp_right=False)
+  if opt.mode == "save":
+    feature_net, stereo_net = load_networks(opt)
+    loader = DataLoader(dataset, opt.batch_size, False, num_workers=opt.batch_size, pin_memory=True, drop_last=False)
+    save_outputs(feature_net, stereo_net, loader, save_folder, opt.batch_size, opt)
+  elif opt.mode == "video":
+    write_video_frames(dataset, save_folder, paths.output_folder("video"), opt.frames)
+  elif opt.mode == "eval":
+    feature_net, stereo_net = load_networks(opt)
+    opt.stereonet_input_scale = 0
+    loader = DataLoader(dataset, opt.batch_size, False, num_workers=opt.batch_size, pin_memory=True, drop_last=False)
+    print(evaluate(feature_net, stereo_net, loader, opt))
+  else:
+    raise NotImplementedError()
+
+
+def make_parser():
+  """The reference's flags and defaults; the viewer flags (max_disp_viz, window_sf, wait, save_disp_as_image) are accepted and
+  unused, as playback is."""
+  p = argparse.ArgumentParser(description="Saved predictions, per-frame images and metrics of a trained StereoNet")
+  p.add_argument("--mode", type=str, choices=["save", "playback", "eval", "video"])
+  p.add_argument("--dataset_path", type=str, help="root folder of the dataset")
+  p.add_argument("--dataset_name", type=str, help="dataset loader to use")
+  p.add_argument("--split", type=str, help="folder of split files")
+  p.add_argument("--subsplit", choices=["train", "val", "test"], help="which lines file of the split")
+  p.add_argument("--load_weights_folder", default=None, type=str, help="folder holding feature_net.pth and stereo_net.pth")
+  p.add_argument("--stereonet_k", type=int, default=3, choices=[3, 4], help="the cost volume is built at 1 / 2^k resolution")
+  p.add_argument("--scales", type=int, nargs="+", default=[0], help="pyramid levels the dataset yields")
+  p.add_argument("--batch_size", type=int, default=8)
+  p.add_argument("--height", type=int, default=512, help="a multiple of 64")
+  p.add_argument("--width", type=int, default=960, help="a multiple of 64")
+  p.add_argument("--max_disp_viz", type=float, default=300)
+  p.add_argument("--window_sf", type=float, default=1.5)
+  p.add_argument("--wait", default=False, action="store_true")
+  p.add_argument("--frames", default=-1, type=int, help="stop --mode video after this many frames (-1: all)")
+  p.add_argument("--save_disp_as_image", action="store_true", default=False)
+  return p
+
+
+if __name__ == "__main__":
+  main(make_parser().parse_args())

@@ -129,14 +129,21 @@ def log_scalars(writer, metrics, losses, examples_per_sec, epoch, step):
     print("LOSS    // " + " | ".join("{}={:.3f}".format(k, float(v)) for k, v in losses.items()))
 
 
-def log_images(writer, inputs, outputs, step, skip_prefixes=("cost_volume",)):
+def log_images(writer, inputs, outputs, step, skip_prefixes=("cost_volume",), disp_cmap=None):
+  """disp_cmap None: every image is logged as it is.  A colour map (a packaged name or a Colormap object): entries whose name
+  contains "disp" are colour-mapped on the device over their own range first, as the reference's train.py:60-71 does on the
+  host with magma; [3,H,W] fp32."""
   if writer is None:
     return
   for io in (inputs, outputs):
     for name in io:
       if any(p in name for p in skip_prefixes):
         continue
-      writer.add_image(name, io[name][0].detach().float().cpu(), step)
+      image = io[name][0].detach().float()
+      if disp_cmap is not None and "disp" in name:
+        from adaptive_stereo.utils.visualization import colormap
+        image = colormap(image.reshape((1, 1) + tuple(image.shape[-2:])), cmap=disp_cmap, out="f32")[0]
+      writer.add_image(name, image.cpu(), step)
 
 
 def save_models(feature_net, stereo_net, optimizer, log_path, epoch):

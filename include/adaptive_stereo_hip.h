@@ -775,6 +775,48 @@ int as_lidar_resolve(uint32_t* zbuf, int B, int H, int W, int i0, int j0, int h,
                      float* depth_out, float* disp_out, uint16_t* disp_u16, const float* pred, float* metrics, void* workspace,
                      int32_t* overflow, void* stream);
 
+/* ---- colour-mapped disparity and error images (csrc/visualize.hip) — utils/visualization.py ------------------------------
+ * What the reference computes on the host per image (apply_cmap :115-158 through matplotlib's Colormap.__call__, then
+ * float_image_to_cv_uint8 :161-178): x [B][1][H][W] fp32, or |y - x| formed on the fly when y is not NULL, is normalised per image
+ * and looked up in a table.  B <= 65535, B*H*W <= 2^30.
+ *
+ * The arithmetic, every operation a single IEEE fp32 operation in the written order:
+ *   v   = x, or fabsf(y - x)
+ *   lo, den: `automatic` is a mask, bit 0 = lo is the minimum of the image's v, bit 1 = hi is its maximum (both as torch.min /
+ *         torch.max: a NaN in the image is a NaN in both).  automatic == 0: lo and den are used as passed and hi is ignored —
+ *         the caller passes lo = (float)vmin, den = (float)((double)vmax - (double)vmin), which is what the reference's Python
+ *         floats give and NOT (float)vmax - (float)vmin.  Otherwise the fixed one of lo, hi is used as passed, den = hi - lo and
+ *         the passed den is ignored.
+ *   n   = (v - lo) / den        a correctly rounded division, never a multiplication by a reciprocal
+ *   t   = n * (float)N
+ *   idx = N + 2 (bad) when t is NaN; N - 1 when t == N; N (under) when t < 0; N + 1 (over) when t > N; else (int)t.
+ *   So -0.0 is entry 0, a constant image with automatic bounds is 0/0 = bad in every pixel (the reference's black image), an
+ *   image holding +inf with automatic bounds has its finite pixels at entry 0 and the infinite one bad.
+ * table: device pointer to N + 3 entries (1 <= N <= 256; then under, over, bad), 4-byte aligned, copied to LDS by every
+ *   workgroup: uint8 [N+3][4] (r, g, b, unused) for the u8 modes, fp32 [N+3][4] (r, g, b, a) for f32; may be NULL for index.
+ * mode and out:
+ *   0  u8 RGB   out [B][H][W][3] uint8, 4-byte aligned (AS_ERR_ARG otherwise).  The batch is ONE byte stream stored in whole
+ *   1  u8 BGR   dwords; image b starts at byte b*H*W*3, which is odd for odd H*W, and a dword that straddles two images carries
+ *               each image's own range.
+ *   2  f32      out [B][3][H][W] fp32 planes r, g, b
+ *   3  index    out [B][H][W] int16 = idx
+ * as_colormap_range writes P = min(64, ceil(H*W / 4096)) (min, max) fp32 pairs per image into workspace
+ * (as_colormap_workspace(B, H*W) BYTES, 4-byte aligned; -1 for a shape outside the limits): no float atomics, and no finalize
+ * launch — as_colormap_apply folds the P pairs of an image itself.  A call with both bounds fixed is one launch, one with an
+ * automatic bound is as_colormap_range + as_colormap_apply with the same x, y and shape; neither synchronises.
+ *
+ * as_image_to_cv: the conversions without a colour map (tensor_to_cv_rgb :47-58, _gray :61-72, _disp :25-44).
+ *   in [B][C][H][W] fp32, C = 1 or 3 -> out [B][H][W][C], channels reversed when flip (RGB -> BGR).
+ *   t = 255.0f * v; when div != 0, t = t / div (a second, separately rounded operation; tensor_to_cv_disp passes (float)W).
+ *   out_f32: out holds t as fp32.  Otherwise uint8 = trunc(t) SATURATED to 0 .. 255, NaN = 0: the reference's
+ *   astype(np.uint8) is unspecified outside 0 .. 255 (it wraps on some hosts), so only in-range values are comparable.
+ *   out 4-byte aligned; B*H*W*C <= 2^30. */
+int64_t as_colormap_workspace(int B, int64_t pixels_per_image);
+int as_colormap_range(const float* x, const float* y, int B, int H, int W, void* workspace, void* stream);
+int as_colormap_apply(const float* x, const float* y, int B, int H, int W, int automatic, float lo, float hi, float den,
+                      const void* workspace, const void* table, int N, int mode, void* out, void* stream);
+int as_image_to_cv(const float* in, int B, int C, int H, int W, int flip, float div, int out_f32, void* out, void* stream);
+
 /* ---- measurement hook (bench.py roofline leg) -----------------------------------
  * When enabled, as_conv32_fwd and as_conv32_wgrad bracket their main kernel with HIP events on the
  * launch stream and account its algorithmic FLOPs (2 * voxels * 32 * 32 * taps).  Kernel ids:

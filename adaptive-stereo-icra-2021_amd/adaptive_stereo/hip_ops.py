@@ -4,7 +4,6 @@ Each Function is a hand-written forward AND backward: autograd only stitches the
 together.  Nothing here computes on the CPU; every call goes through
 ``_native.call`` on the current HIP stream with raw device pointers.
 """
-import os
 import torch
 
 from . import _native as nat
@@ -185,10 +184,14 @@ def flush_deferred_reductions():
 _TAIL_BNSUMS = True        # conv2d_out's data gradient also sums for the last block's BatchNorm backward
 _HEAD_PROJ = True          # conv2d_feature backward: per-tap projections instead of g_z
 _FWD_ACT = True            # full-resolution training forward: previous BatchNorm + LeakyReLU applied on the way in
-_WINOGRAD = os.environ.get("AS_DIAG_DIRECT_FORM") != "1"   # ... and its 3x3 convolution by the minimal-filtering algorithm
-                           # F(2x2, 3x3) (csrc/conv32_wino.hip); the variable is for A/B diagnostics, set_winograd() the API
-# (module switches, each with a setter: tests/test_gpu_end_to_end.py runs both routes and compares them; timing A/B of a
-# route is a tool's business — tests/tools/ab_switch.py — not the environment's)
+_WINOGRAD = True           # ... and its 3x3 convolution by the minimal-filtering algorithm F(2x2, 3x3) (csrc/conv32_wino.hip)
+# (module switches, each with a setter; the off side of each is also the route for shapes its kernel does not take or for
+# cross-replica BatchNorm.  Tests that run both sides of one and compare them: tests/test_gpu_end_to_end.py's
+# test_direct_gradient_accumulation_equals_autograd_accumulation (set_direct_grad_accumulation; it also runs set_head_proj and
+# set_tail_bnsums off) and test_deferred_weight_gradient_reductions_equal_the_immediate_ones (set_defer_reduce),
+# tests/test_gpu_modules.py's trunk against the generic kernels (set_trunk), tests/test_gpu_kernels.py's rolling-window
+# aggregation against the first generation (set_agg3d).  The kernels behind the others are held to each other through the C ABI
+# in tests/test_gpu_kernels.py; timing A/B of a route is a tool's business: tests/tools/ab_switch.py)
 
 
 def set_tail_bnsums(enabled):
@@ -232,16 +235,6 @@ def set_fwd_act(enabled):
 
 
 _WINOGRAD_BWD = True       # (diagnostics: False keeps the direct fused backward while the forward uses minimal filtering)
-_WINOGRAD_BWD_ONE_LAUNCH = True   # both gradients of a layer in ONE launch (csrc/conv32_wino_bwd.hip); False: data gradient, then
-                                  # weight gradient, g_z through HBM in between (as_conv32_wino_bwd) — A/B runs and parity tests
-
-
-def set_winograd_bwd_one_launch(flag: bool):
-  """Switches the minimal-filtering backward of the full-resolution layers between the one-launch kernel and the two launches
-  it replaced (same g_x bit for bit, dW to summation order); returns the previous setting."""
-  global _WINOGRAD_BWD_ONE_LAUNCH
-  prev, _WINOGRAD_BWD_ONE_LAUNCH = _WINOGRAD_BWD_ONE_LAUNCH, bool(flag)
-  return prev
 
 
 def set_winograd(enabled, backward=None):
@@ -251,62 +244,6 @@ def set_winograd(enabled, backward=None):
   prev, _WINOGRAD = _WINOGRAD, bool(enabled)
   _WINOGRAD_BWD = bool(enabled if backward is None else backward)
   return prev
-
-
-# ----------------------------------------------------------------------------------------
-# Weight-gradient kernels beside the data-gradient chain.  In the backward pass of a layer the weight gradient (reads the
-# layer's input and its output gradient, writes private slabs) and the data gradient (reads the output gradient, writes the
-# input gradient the NEXT layer's backward needs) are independent; where neither fills the chip on its own — the strided head
-# (0.23 / 0.56 of the matrix peak), the 3-D aggregation layers (52 + 50 us on 90 K voxels), the 32->1 output layer — the
-# weight gradient CAN be launched on a side stream at the point the output gradient is ready and joined right behind the data
-# gradient: the same kernels, the same bits, in a captured step two parallel branches of the graph.
-# OFF by default: measured on one box, interleaved (profiles/r05_l_ab_wgrad_beside*.txt), the step is not faster with it —
-# 6.91-7.02 ms against 6.80-6.98 at four pairs, 2.52-2.54 against 2.45-2.46 at one: two kernels that each already occupy every
-# CU slow each other down by what the overlap gains, and the fork / join edges add launch latency.  AS_WGRAD_BESIDE=1 or
-# set_wgrad_beside(True) turns it on (tests/test_gpu_end_to_end.py holds it to the one-stream bits).
-# ----------------------------------------------------------------------------------------
-class _Beside(object):
-  enabled = os.environ.get("AS_WGRAD_BESIDE", "0") == "1"
-  stream = None
-  origin = None          # inside a capture: the handle of the stream that may fork (the capture's origin stream)
-  forks = 0
-
-
-def set_wgrad_beside(flag: bool):
-  prev, _Beside.enabled = _Beside.enabled, bool(flag)
-  return prev
-
-
-def set_fork_origin(handle):
-  """OnlineAdapter tells which stream a capture it opened runs on: a fork from an already forked stream inside a capture
-  crashes hipStreamEndCapture on ROCm 7.2, so inside a capture only that stream forks (anywhere else the body runs inline)."""
-  prev, _Beside.origin = _Beside.origin, handle
-  return prev
-
-
-def fork_beside(fn):
-  """Runs fn() — launches that READ what the current stream has produced so far and WRITE only buffers nobody else touches
-  before join_beside() — on the side stream; returns the handle join_beside() takes (None: fn ran inline)."""
-  main = torch.cuda.current_stream()
-  if (not _Beside.enabled or _BN_SYNC is not None or
-      (torch.cuda.is_current_stream_capturing() and main.cuda_stream != _Beside.origin)):
-    fn()
-    return None
-  if _Beside.stream is None:
-    _Beside.stream = torch.cuda.Stream()
-  side = _Beside.stream
-  side.wait_stream(main)
-  with torch.cuda.stream(side):
-    fn()
-  ev = torch.cuda.Event()
-  ev.record(side)
-  _Beside.forks += 1
-  return ev
-
-
-def join_beside(ev):
-  if ev is not None:
-    torch.cuda.current_stream().wait_event(ev)
 
 
 def _rmw_wait(t):
@@ -324,6 +261,32 @@ def _rmw_done(t):
     ev.record(cur)
     _RmwOrder.last[t.data_ptr()] = (cur.cuda_stream, ev)
     _RmwOrder.streams[cur.cuda_stream] = cur
+
+
+class _rmw(object):
+  """``with _rmw(t): call(...)``: the launch inside updates ``t`` in place — ordered behind the last such update from another
+  stream on entry, recorded for the next one on exit.  Nothing for None or outside a multi-stream region."""
+  __slots__ = ("t",)
+
+  def __init__(self, t):
+    self.t = t
+
+  def __enter__(self):
+    _rmw_wait(self.t)
+
+  def __exit__(self, *exc):
+    _rmw_done(self.t)
+
+
+def _grad_dest(sink_w, sink_b, shape_w, shape_b, device):
+  """Where a kernel's (weight, bias)-like gradient pair goes: ``(w, b, accumulate)``.  Both sinks present: the sinks themselves
+  and 1 (the kernel adds, the Function returns None for both); otherwise two fresh tensors of the given shapes and 0 (they go
+  back to autograd) — never one of each, a kernel has one flag.  ``shape_b`` None: a layer without bias, b is None either way.
+  Ordering (_rmw) and workspace lifetime (_keep_for_deferred_reduce) stay with the caller."""
+  if sink_w is not None and (sink_b is not None or shape_b is None):
+    return sink_w, (sink_b if shape_b is not None else None), 1
+  return (torch.empty(shape_w, dtype=torch.float32, device=device),
+          torch.empty(shape_b, dtype=torch.float32, device=device) if shape_b is not None else None, 0)
 
 
 def join_region_streams():
@@ -539,23 +502,15 @@ def conv32_wgrad(x, gin: Pcl, gz, gout: Pcl, shape: ConvShape, want_bias=True, s
   """Returns (dW, db); an entry is None when it was accumulated into its sink instead."""
   lib = nat.load()
   dev = x.device
-  taps = shape.taps()
-  if sink_w is not None and (sink_b is not None or not want_bias):
-    ws = _empty(lib.as_conv32_wgrad_workspace(gin, gout, shape), dev)
-    _keep_for_deferred_reduce(ws)
-    _rmw_wait(sink_w)
-    call("as_conv32_wgrad", ptr(x), gin, ptr(gz), gout, shape, ptr(sink_w), ptr(sink_b), 1, ptr(ws), stream())
-    _rmw_done(sink_w)
-    return None, None
   ws = _empty(lib.as_conv32_wgrad_workspace(gin, gout, shape), dev)
-  if shape.kd > 1:
-    dW = _empty(32 * 32 * taps, dev).view(32, 32, shape.kd, shape.kh, shape.kw)
-  else:
-    dW = _empty(32 * 32 * taps, dev).view(32, 32, shape.kh, shape.kw)
-  db = _empty(32, dev) if want_bias else None
+  shape_w = (32, 32, shape.kd, shape.kh, shape.kw) if shape.kd > 1 else (32, 32, shape.kh, shape.kw)
+  dW, db, acc = _grad_dest(sink_w, sink_b, shape_w, (32,) if want_bias else None, dev)
+  if acc:
+    _keep_for_deferred_reduce(ws)
   # (accumulate = 0: the library reduces right away even inside a deferral region — autograd reads dW on return)
-  call("as_conv32_wgrad", ptr(x), gin, ptr(gz), gout, shape, ptr(dW), ptr(db), 0, ptr(ws), stream())
-  return dW, db
+  with _rmw(dW if acc else None):
+    call("as_conv32_wgrad", ptr(x), gin, ptr(gz), gout, shape, ptr(dW), ptr(db), acc, ptr(ws), stream())
+  return (None, None) if acc else (dW, db)
 
 
 class BnState(object):
@@ -611,11 +566,10 @@ def bn_train_stats(stats: StatParts, gamma, beta, running_mean, running_var):
   st = BnState(gamma.device)
   if _BN_SYNC is not None:
     stats = _gathered_stats(stats, _BN_SYNC)
-  _rmw_wait(running_mean)
-  call("as_bn_finalize", ptr(stats.mean), ptr(stats.m2), ptr(stats.cnt), stats.nparts, ptr(gamma), ptr(beta),
-       ptr(running_mean), ptr(running_var), BN_MOMENTUM, BN_EPS, ptr(st.mean), ptr(st.invstd),
-       ptr(st.scale), ptr(st.shift), stream())
-  _rmw_done(running_mean)
+  with _rmw(running_mean):
+    call("as_bn_finalize", ptr(stats.mean), ptr(stats.m2), ptr(stats.cnt), stats.nparts, ptr(gamma), ptr(beta),
+         ptr(running_mean), ptr(running_var), BN_MOMENTUM, BN_EPS, ptr(st.mean), ptr(st.invstd),
+         ptr(st.scale), ptr(st.shift), stream())
   return st
 
 
@@ -648,13 +602,8 @@ def bn_bwd_coefs(g_a, z, st: BnState, gamma, g: Pcl, train: bool, g_gamma, g_bet
   """Stages 1-2 of the BatchNorm backward (stage 1 may already be in ``sums``): parameter gradients into g_gamma /
   g_beta, stage-3 coefficients left in ``ws`` at as_bn_bwd_coef_offset()."""
   sync = _BN_SYNC if train else None
-  if accumulate:
-    _rmw_wait(g_gamma)
-  try:
+  with _rmw(g_gamma if accumulate else None):
     _bn_bwd_coefs(g_a, z, st, gamma, g, train, g_gamma, g_beta, accumulate, ws, sums, sync)
-  finally:
-    if accumulate:
-      _rmw_done(g_gamma)
 
 
 def _bn_bwd_coefs(g_a, z, st, gamma, g, train, g_gamma, g_beta, accumulate, ws, sums, sync):
@@ -683,25 +632,18 @@ def bn_act_bwd(g_a, z, st: BnState, gamma, g: Pcl, train: bool, sink_gamma=None,
   dev = z.device
   g_z = POOL.get(g, dev)
   ws = sums.workspace if sums is not None else _empty(lib.as_bn_bwd_workspace(g), dev)
+  g_gamma, g_beta, acc = _grad_dest(sink_gamma, sink_beta, (32,), (32,), dev)
   if train and _BN_SYNC is not None:
-    sunk = sink_gamma is not None and sink_beta is not None
-    g_gamma, g_beta = (sink_gamma, sink_beta) if sunk else (_empty(32, dev), _empty(32, dev))
-    bn_bwd_coefs(g_a, z, st, gamma, g, train, g_gamma, g_beta, sunk, ws, sums)
+    bn_bwd_coefs(g_a, z, st, gamma, g, train, g_gamma, g_beta, acc, ws, sums)
     call("as_bn_bwd_apply", ptr(g_a), ptr(z), ptr(st.scale), ptr(st.shift), ptr(st.mean), LEAKY_SLOPE, ptr(g_z), ptr(ws),
          g, stream())
-    return (g_z, None, None) if sunk else (g_z, g_gamma, g_beta)
-  fn = "as_bn_act_bwd_given" if sums is not None else "as_bn_act_bwd"
-  tail = (ptr(ws), g, sums.nparts, stream()) if sums is not None else (ptr(ws), g, stream())
-  if sink_gamma is not None and sink_beta is not None:
-    _rmw_wait(sink_gamma)
-    call(fn, ptr(g_a), ptr(z), ptr(st.scale), ptr(st.shift), ptr(st.mean), ptr(st.invstd), ptr(gamma),
-         LEAKY_SLOPE, int(train), ptr(g_z), ptr(sink_gamma), ptr(sink_beta), 1, *tail)
-    _rmw_done(sink_gamma)
-    return g_z, None, None
-  g_gamma, g_beta = _empty(32, dev), _empty(32, dev)
-  call(fn, ptr(g_a), ptr(z), ptr(st.scale), ptr(st.shift), ptr(st.mean), ptr(st.invstd), ptr(gamma),
-       LEAKY_SLOPE, int(train), ptr(g_z), ptr(g_gamma), ptr(g_beta), 0, *tail)
-  return g_z, g_gamma, g_beta
+  else:
+    fn = "as_bn_act_bwd_given" if sums is not None else "as_bn_act_bwd"
+    tail = (ptr(ws), g, sums.nparts, stream()) if sums is not None else (ptr(ws), g, stream())
+    with _rmw(g_gamma if acc else None):
+      call(fn, ptr(g_a), ptr(z), ptr(st.scale), ptr(st.shift), ptr(st.mean), ptr(st.invstd), ptr(gamma),
+           LEAKY_SLOPE, int(train), ptr(g_z), ptr(g_gamma), ptr(g_beta), acc, *tail)
+  return (g_z, None, None) if acc else (g_z, g_gamma, g_beta)
 
 
 def conv32_dgrad_bnbwd(g_z, g: Pcl, wp_t, shape: ConvShape, residual, next_z, next_st: BnState):
@@ -796,7 +738,6 @@ def block_backward(g_out, x, z, st, w, gamma, g: Pcl, shape: ConvShape, train, s
   data gradient and returned as next_sums (None when not available)."""
   sw, sb, sg, sbeta = sinks if sinks is not None else (None, None, None, None)
   lib = nat.load()
-  beside = None
   all_sunk = sw is not None and sb is not None and sg is not None and sbeta is not None
   if _BWD_FUSED and all_sunk and skip and need_dx and train and next_bn is not None and _BN_SYNC is None and \
       lib.as_conv32_bwd_fused_ok(g, g, shape) == 1:
@@ -811,38 +752,24 @@ def block_backward(g_out, x, z, st, w, gamma, g: Pcl, shape: ConvShape, train, s
     nws = _empty(lib.as_bn_bwd_workspace(g), dev)
     next_z, next_st = next_bn
     if _WINOGRAD and _WINOGRAD_BWD and lib.as_conv32_wino_ok(g, g, shape) == 1:
-      # both gradients by minimal filtering (csrc/conv32_wino.hip MODE 2, csrc/conv32_wino_wgrad.hip): 4 matrix products per
-      # pixel and gradient instead of 9; g_z makes one round trip through HBM between the two launches
+      # both gradients by minimal filtering, 4 matrix products per pixel and gradient instead of 9, in one launch
+      # (csrc/conv32_wino_bwd.hip): g_z stays in LDS between the data-gradient and the weight-gradient waves
       ww_t = pack_special(w, PACK_WINO_T, 16, 16 * 1024,
                           lambda w_, o_: call("as_conv32_wino_pack_weights", ptr(w_), ptr(o_), 1, stream()))
-      if _WINOGRAD_BWD_ONE_LAUNCH:
-        # ... in one launch (csrc/conv32_wino_bwd.hip): g_z stays in LDS between the data-gradient and the weight-gradient waves
-        wws = _empty(lib.as_conv32_wino_bwd_fused_workspace(), dev)
-        _keep_for_deferred_reduce(wws)
-        _rmw_wait(sw)
+      wws = _empty(lib.as_conv32_wino_bwd_fused_workspace(), dev)
+      _keep_for_deferred_reduce(wws)
+      with _rmw(sw):
         call("as_conv32_wino_bwd_fused", ptr(x), g, ptr(g_out), ptr(z), g, shape, ptr(ww_t), ptr(st.scale), ptr(st.shift),
              ptr(st.mean), ptr(coef), LEAKY_SLOPE, ptr(next_z), ptr(next_st.scale), ptr(next_st.shift), ptr(next_st.mean),
              ptr(g_x), ptr(sw), ptr(sb), 1, ptr(nws), ptr(wws), stream())
-        _rmw_done(sw)
-        return g_x, None, None, None, None, BnBwdSums(nws, lib.as_conv32_wino_bwd_fused_parts())
-      wws = _empty(lib.as_conv32_wino_bwd_workspace(), dev)
-      _keep_for_deferred_reduce(wws)
-      g_z = POOL.get(g, dev)
-      _rmw_wait(sw)
-      call("as_conv32_wino_bwd", ptr(x), g, ptr(g_out), ptr(z), g, shape, ptr(ww_t), ptr(st.scale), ptr(st.shift), ptr(st.mean),
-           ptr(coef), LEAKY_SLOPE, ptr(next_z), ptr(next_st.scale), ptr(next_st.shift), ptr(next_st.mean), ptr(g_z), ptr(g_x),
-           ptr(sw), ptr(sb), 1, ptr(nws), ptr(wws), stream())
-      _rmw_done(sw)
-      POOL.put(g_z, g)
-      return g_x, None, None, None, None, BnBwdSums(nws, lib.as_conv32_wino_bwd_parts())
+      return g_x, None, None, None, None, BnBwdSums(nws, lib.as_conv32_wino_bwd_fused_parts())
     wp_t = pack_weights(w, shape, True)
     wws = _empty(lib.as_conv32_bwd_fused_workspace(), dev)
     _keep_for_deferred_reduce(wws)
-    _rmw_wait(sw)
-    call("as_conv32_bwd_fused", ptr(x), g, ptr(g_out), ptr(z), g, shape, ptr(wp_t), ptr(st.scale), ptr(st.shift), ptr(st.mean),
-         ptr(coef), LEAKY_SLOPE, ptr(next_z), ptr(next_st.scale), ptr(next_st.shift), ptr(next_st.mean), ptr(g_x), ptr(sw),
-         ptr(sb), 1, ptr(nws), ptr(wws), stream())
-    _rmw_done(sw)
+    with _rmw(sw):
+      call("as_conv32_bwd_fused", ptr(x), g, ptr(g_out), ptr(z), g, shape, ptr(wp_t), ptr(st.scale), ptr(st.shift), ptr(st.mean),
+           ptr(coef), LEAKY_SLOPE, ptr(next_z), ptr(next_st.scale), ptr(next_st.shift), ptr(next_st.mean), ptr(g_x), ptr(sw),
+           ptr(sb), 1, ptr(nws), ptr(wws), stream())
     return g_x, None, None, None, None, BnBwdSums(nws, lib.as_conv32_bwd_fused_parts())
   if all_sunk and \
       lib.as_conv32_wgrad_bnapply_ok(g, g, shape) == 1:
@@ -855,19 +782,13 @@ def block_backward(g_out, x, z, st, w, gamma, g: Pcl, shape: ConvShape, train, s
     g_z = POOL.get(g, dev)
     wws = _empty(lib.as_conv32_wgrad_workspace(g, g, shape), dev)
     _keep_for_deferred_reduce(wws)
-    _rmw_wait(sw)
-    call("as_conv32_wgrad_bnapply", ptr(x), g, ptr(g_out), ptr(z), g, shape, ptr(st.scale), ptr(st.shift), ptr(st.mean),
-         ptr(coef), LEAKY_SLOPE, ptr(g_z), ptr(sw), ptr(sb), 1, ptr(wws), stream())
-    _rmw_done(sw)
+    with _rmw(sw):
+      call("as_conv32_wgrad_bnapply", ptr(x), g, ptr(g_out), ptr(z), g, shape, ptr(st.scale), ptr(st.shift), ptr(st.mean),
+           ptr(coef), LEAKY_SLOPE, ptr(g_z), ptr(sw), ptr(sb), 1, ptr(wws), stream())
     g_gamma = g_beta = dW = db = None
   else:
     g_z, g_gamma, g_beta = bn_act_bwd(g_out, z, st, gamma, g, train, sg, sbeta, sums)
-    if sw is not None and sb is not None and need_dx:
-      # (sunk gradients: nothing comes back to autograd) beside the data gradient below
-      dW = db = None
-      beside = fork_beside(lambda: conv32_wgrad(x, g, g_z, g, shape, True, sw, sb))
-    else:
-      dW, db = conv32_wgrad(x, g, g_z, g, shape, True, sw, sb)
+    dW, db = conv32_wgrad(x, g, g_z, g, shape, True, sw, sb)
   g_x, next_sums = None, None
   if need_dx:
     wp_t = pack_weights(w, shape, True)
@@ -880,7 +801,6 @@ def block_backward(g_out, x, z, st, w, gamma, g: Pcl, shape: ConvShape, train, s
       g_x = agg3d(g_z, g, wp_t, None, epilogue=2)            # rolling-window kernel: the data gradient of a 3-D layer
     else:
       g_x = conv32(g_z, g, wp_t, None, g, shape, residual=g_out if skip else None)
-  join_beside(beside)
   POOL.put(g_z, g)
   return g_x, dW, db, g_gamma, g_beta, next_sums
 
@@ -909,14 +829,12 @@ def set_bwd_fused(flag: bool):
 
 
 # Who merges a train-mode BatchNorm's per-workgroup partials: the consuming kernel (up to this many partials) or a finalize
-# launch in front of it.  Measured inside a step at 4 pairs, same box, interleaved (tests/tools/ab_env_step.sh,
-# profiles/r05_u_ab_*_merge.txt):
+# launch in front of it.  Measured inside a step at 4 pairs, same box, interleaved (profiles/r05_u_ab_*_merge.txt):
 #   the tail kernel (one wave per SIMD, 234 workgroups, each merging on its own): 38.9 us merging itself against 7.6 + 22.4 us
-#     with a finalize launch -> the launch wins by 9 us: 0;
+#     with a finalize launch -> the launch wins by 9 us: the tail always takes the finalize launch;
 #   aggregation layers 2-4: 71.0 us merging themselves against 7.8 + 62.0 us -> a wash, and a launch boundary more in the replayed
-#     graph: they keep merging (512; beyond that the reads through L2 grow quadratically).
-_TAIL_MERGE_MAX = int(os.environ.get("AS_TAIL_MERGE_MAX", "0"))
-_AGG_MERGE_MAX = int(os.environ.get("AS_AGG_MERGE_MAX", "512"))
+#     graph: they keep merging up to 512 partials (beyond that, k = 3 volumes, the reads through L2 grow quadratically).
+_AGG_MERGE_MAX = 512
 _TAIL_BWD = True         # False: the tail's backward as three launches (as_softargmax_bwd, then as_conv3d_out_bwd's two)
 
 
@@ -952,12 +870,11 @@ class PendingBn(object):
 
   def finalize(self):
     """The same result through the stand-alone finalize launch (no fused consumer available)."""
-    _rmw_wait(self.rm)
     st = self.state
-    call("as_bn_finalize", ptr(self.stats.mean), ptr(self.stats.m2), ptr(self.stats.cnt), self.stats.nparts, ptr(self.gamma),
-         ptr(self.beta), ptr(self.rm), ptr(self.rv), BN_MOMENTUM, BN_EPS, ptr(st.mean), ptr(st.invstd), ptr(st.scale),
-         ptr(st.shift), stream())
-    _rmw_done(self.rm)
+    with _rmw(self.rm):
+      call("as_bn_finalize", ptr(self.stats.mean), ptr(self.stats.m2), ptr(self.stats.cnt), self.stats.nparts, ptr(self.gamma),
+           ptr(self.beta), ptr(self.rm), ptr(self.rv), BN_MOMENTUM, BN_EPS, ptr(st.mean), ptr(st.invstd), ptr(st.scale),
+           ptr(st.shift), stream())
     return st
 
 
@@ -968,14 +885,11 @@ def agg3d(x, g: Pcl, packed_w, bias, z=None, in_state=None, in_bn=None, a_out=No
   partials.  Returns z."""
   z = z if z is not None else POOL.get(g, x.device)
   sm, s2, sc = (stats.mean, stats.m2, stats.cnt) if stats is not None else (None, None, None)
-  if in_bn is not None:
-    _rmw_wait(in_bn.rm)
-  call("as_agg3d_fwd", ptr(x), g, ptr(packed_w), ptr(bias), ptr(in_state.scale) if in_state is not None else None,
-       ptr(in_state.shift) if in_state is not None else None, in_bn.block if in_bn is not None else None, ptr(a_out), ptr(z),
-       int(epilogue), ptr(ep_state.scale) if ep_state is not None else None,
-       ptr(ep_state.shift) if ep_state is not None else None, LEAKY_SLOPE, ptr(sm), ptr(s2), ptr(sc), stream())
-  if in_bn is not None:
-    _rmw_done(in_bn.rm)
+  with _rmw(in_bn.rm if in_bn is not None else None):
+    call("as_agg3d_fwd", ptr(x), g, ptr(packed_w), ptr(bias), ptr(in_state.scale) if in_state is not None else None,
+         ptr(in_state.shift) if in_state is not None else None, in_bn.block if in_bn is not None else None, ptr(a_out), ptr(z),
+         int(epilogue), ptr(ep_state.scale) if ep_state is not None else None,
+         ptr(ep_state.shift) if ep_state is not None else None, LEAKY_SLOPE, ptr(sm), ptr(s2), ptr(sc), stream())
   return z
 
 
@@ -1038,7 +952,7 @@ class CostAggregationFn(torch.autograd.Function):
           zs.append(None); sts.append(st); xs.append(a)
           x = a
       if train:
-        tail_in = (x, prev)                     # z4 + its pending BatchNorm: finalized and applied by the tail kernel
+        tail_in = (x, prev)                     # z4 + its pending BatchNorm: finalized in front of, applied by the tail kernel
     else:
       for l in range(4):
         w, b, gamma, beta = params[4 * l:4 * l + 4]
@@ -1055,19 +969,12 @@ class CostAggregationFn(torch.autograd.Function):
     if tail_in is not None:
       z4, bn4 = tail_in
       if fused_tail:
-        # one launch: layer 4's BatchNorm (merged from its partials) + LeakyReLU on the way in, 32->1 convolution,
+        # one launch: layer 4's BatchNorm (finalized just before) + LeakyReLU on the way in, 32->1 convolution,
         # soft-argmax, arg-max, FCS
         a4 = POOL.get(g, dev) if need_bwd else None
-        if bn4.stats.nparts <= _TAIL_MERGE_MAX:
-          _rmw_wait(bn4.rm)
-          call("as_agg_tail_fwd", ptr(z4), g, None, None, bn4.block, ptr(a4), ptr(w_out), ptr(b_out), LEAKY_SLOPE,
-               ptr(logits), ptr(pred), ptr(argmax), ptr(fcs), stream())
-          _rmw_done(bn4.rm)
-        else:
-          st4 = bn4.finalize()
-          call("as_agg_tail_fwd", ptr(z4), g, ptr(st4.scale), ptr(st4.shift), None, ptr(a4), ptr(w_out), ptr(b_out), LEAKY_SLOPE,
-               ptr(logits), ptr(pred), ptr(argmax), ptr(fcs), stream())
-        keep_alive = bn4                        # (its tensors are referenced by the launch just issued)
+        st4 = bn4.finalize()
+        call("as_agg_tail_fwd", ptr(z4), g, ptr(st4.scale), ptr(st4.shift), None, ptr(a4), ptr(w_out), ptr(b_out), LEAKY_SLOPE,
+             ptr(logits), ptr(pred), ptr(argmax), ptr(fcs), stream())
       else:
         a4 = bn_act(z4, bn4.finalize(), g)
       xs.append(a4)
@@ -1108,23 +1015,20 @@ class CostAggregationFn(torch.autograd.Function):
     w_out = params[16]
     sinks = ctx.sinks
     g_a = POOL.get(g, dev)
-    into_sinks = _sink(sinks, 16) is not None and _sink(sinks, 17) is not None
-    if into_sinks:
-      g_wout, g_bout = sinks[16], sinks[17]
-    else:
-      g_wout, g_bout = torch.empty_like(w_out), _empty(1, dev)
+    g_wout, g_bout, acc = _grad_dest(_sink(sinks, 16), _sink(sinks, 17), w_out.shape, (1,), dev)
+    if not acc:
       grads[16], grads[17] = g_wout, g_bout
     if _TAIL_BWD and lib.as_agg_tail_bwd_ok(g) == 1:
       # soft-argmax backward + both gradients of conv3d_alone in one launch: the logits gradient stays in LDS
       ws = _empty(lib.as_agg_tail_bwd_workspace(g), dev)
       call("as_agg_tail_bwd", ptr(logits), ptr(g_pred), ptr(g_logits_in), ptr(xs[4]), g, ptr(w_out), ptr(g_a), ptr(g_wout),
-           ptr(g_bout), 1 if into_sinks else 0, ptr(ws), stream())
+           ptr(g_bout), acc, ptr(ws), stream())
     else:
       g_logits = torch.empty_like(logits)
       call("as_softargmax_bwd", ptr(logits), ptr(g_pred), ptr(g_logits_in), B, D, H, W, ptr(g_logits), stream())
       ws = _empty(lib.as_conv3d_out_bwd_workspace(g), dev)
-      call("as_conv3d_out_bwd", ptr(g_logits), ptr(xs[4]), g, ptr(w_out), ptr(g_a), ptr(g_wout), ptr(g_bout),
-           1 if into_sinks else 0, ptr(ws), stream())
+      call("as_conv3d_out_bwd", ptr(g_logits), ptr(xs[4]), g, ptr(w_out), ptr(g_a), ptr(g_wout), ptr(g_bout), acc, ptr(ws),
+           stream())
 
     need_feat = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
     for l in range(3, -1, -1):
@@ -1266,10 +1170,9 @@ class FeatureExtractorFn(torch.autograd.Function):
       feats = torch.empty(B, 32, g.H, g.W, dtype=torch.float32, device=dev)
       rms = [bn_buffers[l][0] for l in range(6)]
       rvs = [bn_buffers[l][1] for l in range(6)]
-      _rmw_wait(rms[0])
-      call("as_trunk_finish_fwd", ptr(out), g, ptr(feats), ptr(states), 6, groups, _host_ptrs(rms), _host_ptrs(rvs), BN_MOMENTUM,
-           stream())
-      _rmw_done(rms[0])
+      with _rmw(rms[0]):
+        call("as_trunk_finish_fwd", ptr(out), g, ptr(feats), ptr(states), 6, groups, _host_ptrs(rms), _host_ptrs(rvs),
+             BN_MOMENTUM, stream())
       POOL.put(out, g)
       if not need_bwd:
         for buf in xs[1:] + zs:
@@ -1346,29 +1249,19 @@ class FeatureExtractorFn(torch.autograd.Function):
       gi = geoms[i]
       if i == 0:
         ws = _empty(lib.as_conv4_wgrad_workspace(gi, CONV5_S2), dev)
-        if _sink(sinks, 0) is not None and _sink(sinks, 1) is not None:
-          _rmw_wait(sinks[0])
-          call("as_conv4_wgrad", ptr(ctx.in4), g4, ptr(g_a), gi, CONV5_S2, 3, ptr(sinks[0]), ptr(sinks[1]), 1, ptr(ws),
-               stream())
-          _rmw_done(sinks[0])
-        else:
-          dW = torch.empty_like(wd); db = _empty(32, dev)
-          call("as_conv4_wgrad", ptr(ctx.in4), g4, ptr(g_a), gi, CONV5_S2, 3, ptr(dW), ptr(db), 0, ptr(ws), stream())
+        dW, db, acc = _grad_dest(_sink(sinks, 0), _sink(sinks, 1), wd.shape, (32,), dev)
+        with _rmw(dW if acc else None):
+          call("as_conv4_wgrad", ptr(ctx.in4), g4, ptr(g_a), gi, CONV5_S2, 3, ptr(dW), ptr(db), acc, ptr(ws), stream())
+        if not acc:
           grads[0], grads[1] = dW, db
       else:
         gprev = geoms[i - 1]
-        sw_, sb_ = _sink(sinks, 2 * i), _sink(sinks, 2 * i + 1)
-
-        def head_wgrad(i=i, gprev=gprev, gi=gi, g_a=g_a, sw_=sw_, sb_=sb_):
-          dW, db = conv32_wgrad(levels[i - 1], gprev, g_a, gi, CONV5_S2, True, sw_, sb_)
-          grads[2 * i], grads[2 * i + 1] = dW, db
-        # sunk gradients only: a dW handed back to autograd would be consumed on the main stream
-        ev = fork_beside(head_wgrad) if (sw_ is not None and sb_ is not None) else head_wgrad()
+        grads[2 * i], grads[2 * i + 1] = conv32_wgrad(levels[i - 1], gprev, g_a, gi, CONV5_S2, True,
+                                                      _sink(sinks, 2 * i), _sink(sinks, 2 * i + 1))
         g_prev = POOL.get(gprev, dev)
         wps = pack_special(wd, PACK_S2_DGRAD, 25, 25 * 1024,
                            lambda w_, o_: call("as_conv32_dgrad_s2_pack", ptr(w_), ptr(o_), stream()))
         call("as_conv32_dgrad_s2_packed", ptr(g_a), gi, ptr(wps), ptr(g_prev), gprev, stream())
-        join_beside(ev)
         POOL.put(g_a, gi)
         g_a = g_prev
     POOL.put(g_a, geoms[0])
@@ -1388,60 +1281,39 @@ class FeatureExtractorFn(torch.autograd.Function):
     shape = conv_shape_2d(1)
     parts = lib.as_trunk_parts(g, groups)
     base = 2 * k
-
-    def dest(i, like):
-      s_ = _sink(sinks, base + i)
-      if s_ is not None:
-        return s_, True
-      return torch.empty_like(like), False
-
     bn_grads = torch.empty(6, groups, 2, 32, dtype=torch.float32, device=dev)
     sums = [torch.empty(groups * parts * 64, dtype=torch.float64, device=dev) for _ in range(6)]
     g_a = g_out
     for l in range(6, -1, -1):
       wl, bl = tp[4 * l], tp[4 * l + 1]
-      dW, sunk_w = dest(4 * l, wl)
-      db, sunk_b = dest(4 * l + 1, bl)
-      if sunk_w != sunk_b:                       # one flag for both: fall back to fresh tensors
-        dW, db, sunk_w = torch.empty_like(wl), torch.empty_like(bl), False
+      dW, db, acc = _grad_dest(_sink(sinks, base + 4 * l), _sink(sinks, base + 4 * l + 1), wl.shape, bl.shape, dev)
       ws = _empty(lib.as_trunk_bwd_workspace(g, groups), dev)
-      if sunk_w:
+      if acc:
         _keep_for_deferred_reduce(ws)
-        _rmw_wait(dW)
-      g_x = POOL.get(g, dev)
-      zn, stn, sn = (zs[l - 1], states[l - 1], sums[l - 1]) if l >= 1 else (None, None, None)
-      if l == 6:
-        call("as_trunk_bwd", ptr(g_a), None, None, None, 0, None, None, ptr(xs[6]), ptr(pack_weights(wl, shape, True)), ptr(g_x),
-             ptr(zn), ptr(stn), ptr(sn), g, groups, LEAKY_SLOPE, ptr(dW), ptr(db), int(sunk_w), ptr(ws), stream())
-      else:
-        call("as_trunk_bwd", ptr(g_a), ptr(zs[l]), ptr(states[l]), ptr(sums[l]), parts, ptr(tp[4 * l + 2]), ptr(bn_grads[l]),
-             ptr(xs[l]), ptr(pack_weights(wl, shape, True)), ptr(g_x), ptr(zn), ptr(stn), ptr(sn), g, groups, LEAKY_SLOPE,
-             ptr(dW), ptr(db), int(sunk_w), ptr(ws), stream())
-      if sunk_w:
-        _rmw_done(dW)
-      else:
+      with _rmw(dW if acc else None):
+        g_x = POOL.get(g, dev)
+        zn, stn, sn = (zs[l - 1], states[l - 1], sums[l - 1]) if l >= 1 else (None, None, None)
+        # conv_alone (l = 6) has no BatchNorm behind it: its output gradient is g_a as it stands
+        bn = (ptr(zs[l]), ptr(states[l]), ptr(sums[l]), parts, ptr(tp[4 * l + 2]), ptr(bn_grads[l])) if l < 6 else \
+             (None, None, None, 0, None, None)
+        call("as_trunk_bwd", ptr(g_a), *bn, ptr(xs[l]), ptr(pack_weights(wl, shape, True)), ptr(g_x), ptr(zn), ptr(stn), ptr(sn),
+             g, groups, LEAKY_SLOPE, ptr(dW), ptr(db), acc, ptr(ws), stream())
+      if not acc:
         grads[base + 4 * l], grads[base + 4 * l + 1] = dW, db
       POOL.put(g_a, g)
       if l < 6:
         POOL.put(zs[l], g)
       POOL.put(xs[l + 1] if l < 6 else None, g)
       g_a = g_x
-    gg, gb, all_sunk = [], [], True
-    for l in range(6):
-      d1, s1 = dest(4 * l + 2, tp[4 * l + 2])
-      d2, s2 = dest(4 * l + 3, tp[4 * l + 3])
-      if not (s1 and s2):
-        all_sunk = False
-      gg.append(d1); gb.append(d2)
-    if not all_sunk:
-      gg = [torch.empty_like(tp[4 * l + 2]) for l in range(6)]
-      gb = [torch.empty_like(tp[4 * l + 3]) for l in range(6)]
-    else:
-      _rmw_wait(gg[0])
-    call("as_trunk_finish_bwd", ptr(bn_grads), 6, groups, _host_ptrs(gg), _host_ptrs(gb), int(all_sunk), stream())
-    if all_sunk:
-      _rmw_done(gg[0])
-    else:
+    # the six (gamma, beta) pairs leave in one launch with one flag: into their sinks only when all twelve have one
+    bn_sinks = [(_sink(sinks, base + 4 * l + 2), _sink(sinks, base + 4 * l + 3)) for l in range(6)]
+    if any(s_ is None for pair in bn_sinks for s_ in pair):
+      bn_sinks = [(None, None)] * 6
+    dests = [_grad_dest(sg, sb, tp[4 * l + 2].shape, tp[4 * l + 3].shape, dev) for l, (sg, sb) in enumerate(bn_sinks)]
+    gg, gb, acc = [d[0] for d in dests], [d[1] for d in dests], dests[0][2]
+    with _rmw(gg[0] if acc else None):
+      call("as_trunk_finish_bwd", ptr(bn_grads), 6, groups, _host_ptrs(gg), _host_ptrs(gb), acc, stream())
+    if not acc:
       for l in range(6):
         grads[base + 4 * l + 2], grads[base + 4 * l + 3] = gg[l], gb[l]
     return g_a
@@ -1582,25 +1454,19 @@ class EdgeRefineFn(torch.autograd.Function):
     g_a = POOL.get(g, dev)
     ws = _empty(lib.as_conv32to1_bwd_workspace(g, s33), dev)
     sums = None
-    if _sink(sinks, 28) is not None and _sink(sinks, 29) is not None:
-      if _TAIL_BNSUMS and ctx.train and _BN_SYNC is None and lib.as_conv32to1_bnsums_ok(g, s33) == 1:
-        # the data gradient also leaves stage 1 of the last block's BatchNorm backward behind (its own pass otherwise)
-        nws = _empty(lib.as_bn_bwd_workspace(g), dev)
-        # the weight gradient (reads the last activation and g_pre, adds into its sinks) beside the data gradient
-        ev = fork_beside(lambda: call("as_conv32to1_bwd", ptr(g_pre), ptr(xs[6]), g, s33, ptr(w_out), None, ptr(sinks[28]),
-                                      ptr(sinks[29]), 1, ptr(ws), stream()))
-        call("as_conv32to1_dgrad_bnsums", ptr(g_pre), g, s33, ptr(w_out), ptr(g_a), ptr(zs[5]), ptr(sts[5].scale),
-             ptr(sts[5].shift), ptr(sts[5].mean), LEAKY_SLOPE, ptr(nws), stream())
-        join_beside(ev)
-        sums = BnBwdSums(nws, lib.as_conv32to1_bnsums_parts(g))
-      else:
-        call("as_conv32to1_bwd", ptr(g_pre), ptr(xs[6]), g, s33, ptr(w_out), ptr(g_a), ptr(sinks[28]), ptr(sinks[29]), 1,
-             ptr(ws), stream())
-    else:
-      g_wout, g_bout = torch.empty_like(w_out), _empty(1, dev)
-      call("as_conv32to1_bwd", ptr(g_pre), ptr(xs[6]), g, s33, ptr(w_out), ptr(g_a), ptr(g_wout), ptr(g_bout), 0,
-           ptr(ws), stream())
+    g_wout, g_bout, acc = _grad_dest(_sink(sinks, 28), _sink(sinks, 29), w_out.shape, (1,), dev)
+    if not acc:
       grads[28], grads[29] = g_wout, g_bout
+    # (sinks only) the data gradient on a kernel of its own that also leaves stage 1 of the last block's BatchNorm backward
+    # behind (its own pass otherwise); as_conv32to1_bwd then computes the weight gradient alone (g_x = NULL)
+    split = acc and _TAIL_BNSUMS and ctx.train and _BN_SYNC is None and lib.as_conv32to1_bnsums_ok(g, s33) == 1
+    nws = _empty(lib.as_bn_bwd_workspace(g), dev) if split else None
+    call("as_conv32to1_bwd", ptr(g_pre), ptr(xs[6]), g, s33, ptr(w_out), None if split else ptr(g_a), ptr(g_wout), ptr(g_bout),
+         acc, ptr(ws), stream())
+    if split:
+      call("as_conv32to1_dgrad_bnsums", ptr(g_pre), g, s33, ptr(w_out), ptr(g_a), ptr(zs[5]), ptr(sts[5].scale),
+           ptr(sts[5].shift), ptr(sts[5].mean), LEAKY_SLOPE, ptr(nws), stream())
+      sums = BnBwdSums(nws, lib.as_conv32to1_bnsums_parts(g))
 
     for l in range(5, -1, -1):
       wl, bl, gamma, beta = params[4 + 4 * l:8 + 4 * l]
@@ -1645,12 +1511,10 @@ class EdgeRefineFn(torch.autograd.Function):
     else:
       h_proj = None
       g_z0, g_gamma0, g_beta0 = bn_act_bwd(g_a, ctx.z0, ctx.st0, gamma0, g, ctx.train, _sink(sinks, 2), _sink(sinks, 3), sums)
-      if _sink(sinks, 0) is not None and _sink(sinks, 1) is not None:
-        call("as_conv4_wgrad", ptr(ctx.in4), g4, ptr(g_z0), g, s33, 4, ptr(sinks[0]), ptr(sinks[1]), 1, ptr(ws4), stream())
+      dW0, db0, acc = _grad_dest(_sink(sinks, 0), _sink(sinks, 1), w0.shape, (32,), dev)
+      call("as_conv4_wgrad", ptr(ctx.in4), g4, ptr(g_z0), g, s33, 4, ptr(dW0), ptr(db0), acc, ptr(ws4), stream())
+      if acc:
         dW0 = db0 = None
-      else:
-        dW0 = torch.empty_like(w0); db0 = _empty(32, dev)
-        call("as_conv4_wgrad", ptr(ctx.in4), g4, ptr(g_z0), g, s33, 4, ptr(dW0), ptr(db0), 0, ptr(ws4), stream())
     grads[0:4] = [dW0, db0, g_gamma0, g_beta0]
 
     g_coarse = None

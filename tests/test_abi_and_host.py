@@ -77,6 +77,40 @@ def test_product_refuses_cpu_tensors():
     snet(x, torch.zeros(1, 32, 4, 4), torch.zeros(1, 32, 4, 4), "l")
 
 
+def test_parameter_gradients_go_to_both_sinks_or_to_two_fresh_tensors():
+  """hip_ops._grad_dest decides for every backward kernel with a (weight, bias)-like gradient pair: both sinks and
+  accumulate = 1, or two fresh tensors and accumulate = 0, never one of each; hip_ops._rmw records nothing outside a
+  multi-stream region."""
+  from adaptive_stereo import hip_ops
+  sw, sb = torch.zeros(32, 4, 3, 3), torch.zeros(32)
+  dev = sw.device
+  w, b, acc = hip_ops._grad_dest(sw, sb, sw.shape, sb.shape, dev)
+  assert w is sw and b is sb and acc == 1
+  for sink_w, sink_b in ((None, sb), (sw, None), (None, None)):
+    w, b, acc = hip_ops._grad_dest(sink_w, sink_b, (32, 4, 3, 3), (32,), dev)
+    assert acc == 0
+    assert w.shape == sw.shape and b.shape == sb.shape and w.dtype == b.dtype == torch.float32
+    assert w.is_contiguous() and b.is_contiguous()
+    for fresh in (w, b):
+      assert all(fresh.data_ptr() != s.data_ptr() for s in (sw, sb))
+  # a layer without bias: the weight's sink alone decides, and there is no bias gradient either way
+  w, b, acc = hip_ops._grad_dest(sw, None, sw.shape, None, dev)
+  assert w is sw and b is None and acc == 1
+  w, b, acc = hip_ops._grad_dest(sw, sb, sw.shape, None, dev)
+  assert w is sw and b is None and acc == 1
+  w, b, acc = hip_ops._grad_dest(None, sb, sw.shape, None, dev)
+  assert w.shape == sw.shape and w.data_ptr() != sw.data_ptr() and b is None and acc == 0
+  # ordering: nothing is recorded for None, and nothing while no multi-stream region is open
+  assert hip_ops._RmwOrder.enabled is False and hip_ops._RmwOrder.last == {}
+  ran = []
+  with hip_ops._rmw(None):
+    ran.append(1)
+  with hip_ops._rmw(sw):
+    ran.append(2)
+  assert ran == [1, 2]
+  assert hip_ops._RmwOrder.last == {} and hip_ops._RmwOrder.streams == {}
+
+
 def test_reservoir_is_uniform_like_the_reference():
   """Mirrors the reference's test/test_stereo_reservoir.py: mean of kept items ~ 500 +- 5."""
   random.seed(123)

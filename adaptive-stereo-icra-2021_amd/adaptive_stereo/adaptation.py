@@ -121,10 +121,13 @@ class FlatArena(object):
 class FusedClipAdam(object):
   """clip_grad_norm_(group 0, max_norm) + Adam over the arena (as_sumsq / as_adam_step)."""
 
-  def __init__(self, arena, lr, betas=(0.9, 0.999), eps=1e-8, clip_group=0, max_norm=1.0):
+  def __init__(self, arena, lr, betas=(0.9, 0.999), eps=1e-8, clip_group=0, max_norm=1.0, lr_on_device=False):
     self.arena, self.lr, self.betas, self.eps = arena, lr, betas, eps
     self.clip_group, self.max_norm = clip_group, max_norm
     dev = arena.params.device
+    # lr_on_device: Adam reads the learning rate from a device float (as_adam_step_lr), so that a captured step follows a
+    # schedule through set_lr() without a new capture; off, the launches are as_adam_step with the host value
+    self.lr_dev = torch.full((1,), float(lr), dtype=torch.float32, device=dev) if lr_on_device else None
     self.exp_avg = torch.zeros_like(arena.params)
     self.exp_avg_sq = torch.zeros_like(arena.params)
     self.step_count = 0
@@ -149,6 +152,11 @@ class FusedClipAdam(object):
         nat.call("as_sumsq_clip", nat.ptr(a.grads[s:e]), e - s, float(self.max_norm), nat.ptr(self.sumsq), nat.ptr(self.coef),
                  nat.ptr(self.step_dev) if (ride and gi == 0) else None, nat.ptr(self.ws), nat.stream())
         scale = self.coef
+      if self.lr_dev is not None:
+        nat.call("as_adam_step_lr", nat.ptr(a.params[s:e]), nat.ptr(a.grads[s:e]), nat.ptr(self.exp_avg[s:e]),
+                 nat.ptr(self.exp_avg_sq[s:e]), e - s, nat.ptr(scale), nat.ptr(self.lr_dev), self.betas[0], self.betas[1],
+                 self.eps, self.step_count, nat.ptr(self.step_dev), nat.stream())
+        continue
       nat.call("as_adam_step", nat.ptr(a.params[s:e]), nat.ptr(a.grads[s:e]), nat.ptr(self.exp_avg[s:e]),
                nat.ptr(self.exp_avg_sq[s:e]), e - s, nat.ptr(scale), self.lr, self.betas[0], self.betas[1],
                self.eps, self.step_count, nat.ptr(self.step_dev), nat.stream())
@@ -156,6 +164,13 @@ class FusedClipAdam(object):
   def grad_norm(self):
     """Pre-clip L2 norm of the clipped group at the last step (device scalar)."""
     return torch.sqrt(self.sumsq)
+
+  def set_lr(self, lr):
+    """The learning rate of the following steps.  With lr_on_device a captured step picks it up on its next replay; without,
+    only eager steps see it (a captured as_adam_step node holds the value it was captured with)."""
+    self.lr = float(lr)
+    if self.lr_dev is not None:
+      self.lr_dev.fill_(self.lr)
 
   def state_dict(self):
     """torch.optim.Adam-compatible layout (what the reference writes to adam.pth, train.py:136-137): one
@@ -176,6 +191,41 @@ class FusedClipAdam(object):
       groups.append({"lr": self.lr, "betas": self.betas, "eps": self.eps, "weight_decay": 0, "amsgrad": False,
                      "params": ids})
     return {"state": state, "param_groups": groups}
+
+  def load_state_dict(self, sd):
+    """Inverse of state_dict() (a torch.optim.Adam state of the same parameter groups: adam.pth, train.py --load_adam): both
+    moments into the arena, the step count (one count for every parameter, as one optimizer over all of them has) and the
+    learning rate of the first group.  Parameters without an entry get zero moments."""
+    groups = sd["param_groups"]
+    if len(groups) != len(self.arena.all_params):
+      raise ValueError("FusedClipAdam.load_state_dict: %d parameter groups, this optimizer has %d"
+                       % (len(groups), len(self.arena.all_params)))
+    where = {id(p): (off, n) for _, _, p, off, n in self.arena.entries}
+    self.exp_avg.zero_(); self.exp_avg_sq.zero_()
+    steps = set()
+    for group, listed in zip(groups, self.arena.all_params):
+      if len(group["params"]) != len(listed):
+        raise ValueError("FusedClipAdam.load_state_dict: a group of %d parameters, this optimizer's has %d"
+                         % (len(group["params"]), len(listed)))
+      for index, (name, p, live) in zip(group["params"], listed):
+        st = sd["state"].get(index)
+        if st is None:
+          continue
+        if not live:
+          raise ValueError("FusedClipAdam.load_state_dict: state for %s, which never receives a gradient" % name)
+        off, n = where[id(p)]
+        for key, dst in (("exp_avg", self.exp_avg), ("exp_avg_sq", self.exp_avg_sq)):
+          if tuple(st[key].shape) != tuple(p.shape):
+            raise ValueError("FusedClipAdam.load_state_dict: %s of %s is %s, the parameter %s"
+                             % (key, name, tuple(st[key].shape), tuple(p.shape)))
+          dst[off:off + n].copy_(st[key].reshape(-1).to(torch.float32))
+        steps.add(int(float(st["step"])))
+    if len(steps) > 1:
+      raise ValueError("FusedClipAdam.load_state_dict: parameters at different step counts %s" % sorted(steps))
+    self.step_count = steps.pop() if steps else 0
+    self.step_dev.fill_(float(self.step_count))
+    self.betas, self.eps = tuple(groups[0]["betas"]), groups[0]["eps"]
+    self.set_lr(groups[0]["lr"])
 
 
 class OnlineAdapter(object):

@@ -1763,3 +1763,43 @@ class KhamisLossFn(torch.autograd.Function):
     g_pred = torch.empty_like(pred)
     call("as_khamis_bwd", ptr(pred), ptr(gt), ptr(g), ptr(out2), pred.numel(), ptr(g_pred), stream())
     return g_pred, None
+
+
+# ----------------------------------------------------------------------------------------
+# supervised two-scale loss (train.py:215: khamis_robust_loss_multiscale with scales = [s, s + k])
+# ----------------------------------------------------------------------------------------
+class SupervisedLossFn(torch.autograd.Function):
+  """(pred0 [B,1,H,W], coarse [B,h,w], up [B,1,H,W], gt [B,1,H,W], gain) -> out4 = [khamis(pred0, gt), khamis(up, gt), their sum,
+  max(count(gt > 0), 1)].  ``up`` is gain * bilinear(coarse) as StereoNet.forward materialised it and enters as data: the node
+  sends the coarse term's gradient to ``coarse`` itself, through the up-sampling adjoint (as_khamis2_bwd), so the derivative
+  map at full resolution is never stored.  One pass over gt forward, one launch backward."""
+
+  @staticmethod
+  def forward(ctx, pred0, coarse, up, gt, gain):
+    pred0, coarse, up, gt = f32c(pred0), f32c(coarse), f32c(up), f32c(gt)
+    if not (pred0.shape == up.shape == gt.shape) or pred0.dim() != 4 or pred0.shape[1] != 1:
+      raise RuntimeError("SupervisedLossFn: pred0 %s, up %s and gt %s must all be [B,1,H,W]"
+                         % (tuple(pred0.shape), tuple(up.shape), tuple(gt.shape)))
+    if coarse.dim() != 3 or coarse.shape[0] != pred0.shape[0]:
+      raise RuntimeError("SupervisedLossFn: coarse map %s must be [B,h,w]" % (tuple(coarse.shape),))
+    n = pred0.numel()
+    out4 = _empty(4, pred0.device)
+    ws = _empty(nat.load().as_khamis2_workspace(n), pred0.device)
+    call("as_khamis2_fwd", ptr(pred0), ptr(up), ptr(gt), n, ptr(out4), ptr(ws), stream())
+    ctx.save_for_backward(pred0, up, gt, out4)
+    ctx.dims = (tuple(coarse.shape), float(gain))
+    return out4
+
+  @staticmethod
+  def backward(ctx, g_out4):
+    pred0, up, gt, out4 = ctx.saved_tensors
+    if ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:
+      raise NotImplementedError("SupervisedLossFn: the up-sampled map and the ground truth enter as data")
+    (B, h, w), gain = ctx.dims
+    H, W = pred0.shape[-2:]
+    g = f32c(g_out4)                     # [0..2] are read; the count carries no gradient
+    g_pred0 = torch.empty_like(pred0)
+    g_coarse = torch.empty(B, h, w, dtype=torch.float32, device=pred0.device)
+    call("as_khamis2_bwd", ptr(pred0), ptr(up), ptr(gt), ptr(g), ptr(out4), B, int(H), int(W), h, w, gain, ptr(g_pred0),
+         ptr(g_coarse), stream())
+    return g_pred0, g_coarse, None, None, None

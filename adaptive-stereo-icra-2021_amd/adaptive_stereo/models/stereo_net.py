@@ -190,7 +190,9 @@ class StereoNet(nn.Module):
     if output_cost_volume:
       outputs["cost_volume_{}/{}".format(side, coarse_scale)] = logits
     H, W = left_img.shape[-2:]
-    outputs["pred_disp_{}/{}".format(side, coarse_scale)] = hip_ops.UpsampleBilinearFn.apply(
-        pred, H, W, float(2 ** self.k))
+    up = hip_ops.UpsampleBilinearFn.apply(pred, H, W, float(2 ** self.k))
+    up._as_coarse = pred                       # khamis_robust_loss_two_scale back-propagates to the low-resolution map itself
+    up._as_coarse_gain = float(2 ** self.k)
+    outputs["pred_disp_{}/{}".format(side, coarse_scale)] = up
     outputs["pred_disp_{}/{}".format(side, self.input_scale)] = self.edge_aware_refinements[0](pred, left_img)
     return outputs

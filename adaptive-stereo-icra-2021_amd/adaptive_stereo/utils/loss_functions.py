@@ -7,7 +7,7 @@ used by the experience-replay modes (adapt.py:339-349) and the supervised multis
 import torch
 
 from .. import _native as nat
-from ..hip_ops import MonodepthLossFn, KhamisLossFn
+from ..hip_ops import MonodepthLossFn, KhamisLossFn, SupervisedLossFn
 
 
 def monodepth_loss(pred_disp, true_img, warped_img, smoothness_weight=0.001):
@@ -48,6 +48,23 @@ def khamis_robust_loss_multiscale(inputs, outputs, scales=[0], gt_disp_scale=0):
     losses["khamis_robust_loss/{}".format(scale)] = this
     losses["total_loss"] = losses["total_loss"] + this
   return losses
+
+
+def khamis_robust_loss_two_scale(inputs, outputs, scale=0, coarse_scale=3, gt_disp_scale=0):
+  """khamis_robust_loss_multiscale(scales=[scale, coarse_scale]) as ONE autograd node (hip_ops.SupervisedLossFn) over the refined
+  map and the low-resolution soft-argmax output that StereoNet.forward leaves on ``pred_disp_l/{coarse_scale}``: one pass over
+  the ground truth forward, one launch backward.  Same keys as the reference's dictionary.  Outputs that do not carry the
+  low-resolution map (not produced by this package's StereoNet) go through khamis_robust_loss_multiscale."""
+  pred0 = outputs["pred_disp_l/{}".format(scale)]
+  up = outputs["pred_disp_l/{}".format(coarse_scale)]
+  coarse = getattr(up, "_as_coarse", None)
+  if coarse is None:
+    return khamis_robust_loss_multiscale(inputs, outputs, scales=[scale, coarse_scale], gt_disp_scale=gt_disp_scale)
+  gt = inputs["gt_disp_l/{}".format(gt_disp_scale)]
+  nat.require_gpu(pred0, up, coarse, gt)
+  out4 = SupervisedLossFn.apply(pred0, coarse, up.detach(), gt.detach(), up._as_coarse_gain)
+  return {"total_loss": out4[2], "khamis_robust_loss/{}".format(scale): out4[0],
+          "khamis_robust_loss/{}".format(coarse_scale): out4[1]}
 
 
 def monodepth_leftright_loss(left_img, right_img, outputs, warper, scale):

@@ -197,10 +197,14 @@ __device__ inline float clipped_grad(float g, float gs) {
 #pragma clang fp contract(off)
   return g * gs;
 }
+// LR_DEV: the learning rate is *lr_dev (a device float: a captured step follows a schedule without a new capture), else lr.
+template <bool LR_DEV>
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                     float* __restrict__ m, float* __restrict__ v, long n,
-                                                    const float* __restrict__ grad_scale, float lr, float b1, float b2,
+                                                    const float* __restrict__ grad_scale, float lr, const float* __restrict__ lr_dev,
+                                                    float b1, float b2,
                                                     float eps, int step_host, const float* __restrict__ step_dev) {
+  if (LR_DEV) lr = lr_dev[0];
   // bias corrections from the step count: a host integer, or (hipGraph replay) a device counter
   const double step = step_dev ? (double)step_dev[0] : (double)step_host;
   const float bc1 = (float)(1.0 - pow((double)b1, step));
@@ -223,8 +227,20 @@ extern "C" int as_adam_step(float* param, const float* grad, float* exp_avg, flo
   AS_CHECK_ARG(param && grad && exp_avg && exp_avg_sq && n > 0 && (step >= 1 || step_dev), "as_adam_step: bad argument");
   long nb = (n + 255) / 256;
   if (nb > 2048) nb = 2048;
-  hipLaunchKernelGGL(adam_kernel, dim3((int)nb), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq,
-                     (long)n, grad_scale_dev, lr, beta1, beta2, eps, step, step_dev);
+  hipLaunchKernelGGL(adam_kernel<false>, dim3((int)nb), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq,
+                     (long)n, grad_scale_dev, lr, (const float*)nullptr, beta1, beta2, eps, step, step_dev);
   AS_CHECK_LAUNCH("as_adam_step");
+  return AS_OK;
+}
+
+extern "C" int as_adam_step_lr(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
+                               const float* grad_scale_dev, const float* lr_dev, float beta1, float beta2, float eps,
+                               int step, const float* step_dev, void* stream) {
+  AS_CHECK_ARG(param && grad && exp_avg && exp_avg_sq && lr_dev && n > 0 && (step >= 1 || step_dev), "as_adam_step_lr: bad argument");
+  long nb = (n + 255) / 256;
+  if (nb > 2048) nb = 2048;
+  hipLaunchKernelGGL(adam_kernel<true>, dim3((int)nb), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq,
+                     (long)n, grad_scale_dev, 0.f, lr_dev, beta1, beta2, eps, step, step_dev);
+  AS_CHECK_LAUNCH("as_adam_step_lr");
   return AS_OK;
 }

@@ -1,13 +1,24 @@
-"""The part of the reference's train.py that other scripts import (adapt.py:13, evaluate_model.py:10):
-TrainOptions, process_batch, evaluate, log_scalars, log_images, save_models — SURVEY.md §8b / §8f-3.
+"""The reference's train.py: supervised StereoNet training (train.train, train.py:140-243) and the part other scripts import
+(adapt.py:13, evaluate_model.py:10): TrainOptions, process_batch, evaluate, log_scalars, log_images, save_models —
+SURVEY.md §8b / §8f-3.
+
+``train`` is the reference's loop: seed 123, opt.json, the two StereoDatasets with scales [s, s + k] (random crop and optional
+flip for training), the evaluate / log_scalars / log_images cadence, a checkpoint per ``save_freq`` epochs from epoch 1 on and
+one at the end, StepLR(scheduler_step_size, 0.5).  The step itself is adaptive_stereo.training.SupervisedTrainer: the two-scale
+Khamis loss as one fused node, clip + Adam over flat arenas, the whole step one captured hipGraph from the second full batch on
+(the schedule reaches it through a device scalar; a last, smaller batch of an epoch runs eagerly).  ``--load_weights_folder``
+and ``--load_adam`` resume from a checkpoint folder (with ``--load_adam`` at the checkpoint's learning rate).  tensorboardX
+and gitpython are optional: without a writer only the console summary is printed, and the commit hash in opt.json comes from
+``git rev-parse HEAD`` or is "unknown".
 
 ``evaluate`` keeps the reference's definition of the metrics (train.py:74-126: per-batch EPE over gt>0,
 D1-all at 2/3/4/5 px, FCS mean; then the mean over batches) but computes each batch's reductions in one
 fused kernel (as_eval_metrics) and reads nothing back until the loop has finished.
-Supervised training itself (train.train) and the dataset layer are out of scope.
 """
 import argparse
+import json
 import os
+import time
 
 import torch
 
@@ -162,3 +173,106 @@ def load_models(feature_net, stereo_net, folder, strict=True):
   """adapt.py:203-206."""
   feature_net.load_state_dict(torch.load(os.path.join(folder, "feature_net.pth"), map_location="cpu"), strict=strict)
   stereo_net.load_state_dict(torch.load(os.path.join(folder, "stereo_net.pth"), map_location="cpu"), strict=strict)
+
+
+def _commit_hash():
+  import subprocess
+  try:
+    r = subprocess.run(["git", "rev-parse", "HEAD"], cwd=os.path.dirname(os.path.abspath(__file__)), capture_output=True,
+                       text=True, timeout=10)
+    sha = r.stdout.strip()
+    return sha if r.returncode == 0 and sha else "unknown"
+  except (OSError, subprocess.SubprocessError):
+    return "unknown"
+
+
+def _summary_writer(path):
+  try:
+    from tensorboardX import SummaryWriter
+  except ImportError:
+    print("tensorboardX is not installed: console summaries only")
+    return None
+  return SummaryWriter(path)
+
+
+def train(opt, train_dataset=None, val_dataset=None, writer=None):
+  """Reference train.py:140-243.  ``train_dataset`` / ``val_dataset`` (map-style datasets of the StereoDataset sample
+  dictionary) and ``writer`` (add_scalar / add_image) replace what the options would build.  Returns the SupervisedTrainer."""
+  from torch.utils.data import DataLoader
+  from adaptive_stereo.models.stereo_net import StereoNet, FeatureExtractorNetwork
+  from adaptive_stereo.training import SupervisedTrainer
+
+  torch.manual_seed(123)
+  log_path = os.path.join(opt.log_dir, opt.model_name)
+  os.makedirs(log_path, exist_ok=True)
+  opt.commit_hash = _commit_hash()
+  with open(os.path.join(log_path, "opt.json"), "w") as f:
+    opt_readable = json.dumps(opt.__dict__, sort_keys=True, indent=2)
+    print("TRAINING OPTIONS:\n" + opt_readable)
+    f.write(opt_readable + "\n")
+
+  s, k = opt.stereonet_input_scale, opt.stereonet_k
+  feature_net = FeatureExtractorNetwork(k).cuda()
+  stereo_net = StereoNet(k, 1, s).cuda()
+  if opt.load_weights_folder is not None:
+    print("Loading models from: ", opt.load_weights_folder)
+    load_models(feature_net, stereo_net, opt.load_weights_folder, strict=True)
+  trainer = SupervisedTrainer(feature_net, stereo_net, lr=opt.learning_rate, clip_grad_norm=opt.clip_grad_norm)
+  optimizer = trainer.optimizer
+  if opt.load_adam:
+    if opt.load_weights_folder is None:
+      raise ValueError("--load_adam needs --load_weights_folder")
+    optimizer.load_state_dict(torch.load(os.path.join(opt.load_weights_folder, "adam.pth"), map_location="cpu"))
+  base_lr = optimizer.lr
+
+  loss_scales = [s, s + k]
+  if train_dataset is None:
+    from adaptive_stereo.datasets.stereo_dataset import StereoDataset
+    train_dataset = StereoDataset(opt.dataset_path, opt.dataset_name, opt.split, opt.height, opt.width, "train",
+                                  scales=loss_scales, do_hflip=opt.do_hflip, random_crop=True, load_disp_left=True,
+                                  load_disp_right=True)
+  if val_dataset is None:
+    from adaptive_stereo.datasets.stereo_dataset import StereoDataset
+    val_dataset = StereoDataset(opt.dataset_path, opt.dataset_name, opt.split, opt.height, opt.width, "val",
+                                scales=loss_scales, do_hflip=False, random_crop=False, load_disp_left=True,
+                                load_disp_right=False)
+  pin = opt.num_workers > 0
+  train_loader = DataLoader(train_dataset, opt.batch_size, not opt.no_shuffle, num_workers=opt.num_workers, pin_memory=pin,
+                            drop_last=False)
+  val_loader = DataLoader(val_dataset, opt.batch_size, False, num_workers=opt.num_workers, pin_memory=pin, drop_last=False)
+  print("DATASET SIZES:\n  TRAIN={} VAL={}".format(len(train_dataset), len(val_dataset)))
+  if writer is None:
+    writer = _summary_writer(os.path.join(log_path, "val"))
+
+  epoch, step = 0, 0
+  for epoch in range(opt.num_epochs):
+    feature_net.train(); stereo_net.train()
+    for bi, inputs in enumerate(train_loader):
+      t0 = time.time()
+      inputs = {key: value.cuda(non_blocking=True) for key, value in inputs.items()}
+      left, right = inputs["color_l/{}".format(s)], inputs["color_r/{}".format(s)]
+      gt = inputs["gt_disp_l/{}".format(s)]
+      result = trainer.step(left, right, gt)
+      outputs = result["outputs"]
+      losses = {name: value for name, value in result.items() if name != "outputs"}
+      if trainer.graph_count() == 0 and left.shape[0] == opt.batch_size:
+        trainer.capture(left, right, gt)            # after the first full batch; leaves the training state as it is
+      early_phase = (step % opt.log_frequency) == 0 and step < 2000
+      late_phase = (step % 2000) == 0 or (bi == 0)          # at the start of each epoch
+      if early_phase or late_phase:
+        torch.cuda.synchronize()
+        elapsed_this_batch = time.time() - t0
+        metrics = evaluate(feature_net, stereo_net, val_loader, opt)
+        log_scalars(writer, metrics, losses, opt.batch_size / elapsed_this_batch, epoch, step)
+        log_images(writer, inputs, outputs, step)
+      step += 1
+    if epoch >= 1 and (epoch % opt.save_freq) == 0:
+      save_models(feature_net, stereo_net, optimizer, log_path, epoch)
+    trainer.set_lr(base_lr * 0.5 ** ((epoch + 1) // opt.scheduler_step_size))        # StepLR(scheduler_step_size, 0.5).step()
+  save_models(feature_net, stereo_net, optimizer, log_path, epoch)         # a final save after training
+  return trainer
+
+
+if __name__ == "__main__":
+  train(TrainOptions().parse())
+  print("Done with training!")

@@ -643,6 +643,25 @@ int as_sumsq_clip(const float* g, int64_t n, float max_norm, float* out, float* 
 int as_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
                  const float* grad_scale_dev, float lr, float beta1, float beta2, float eps,
                  int step, const float* step_dev, void* stream);
+/* as_adam_step with the learning rate read from *lr_dev (a device float): bit for bit as_adam_step at that lr; a captured step
+ * follows a learning-rate schedule without a new capture. */
+int as_adam_step_lr(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
+                    const float* grad_scale_dev, const float* lr_dev, float beta1, float beta2, float eps,
+                    int step, const float* step_dev, void* stream);
+
+/* ---- supervised two-scale loss — train.py:215, utils/loss_functions.py:18-38 with scales = [s, s + k] ----------
+ * pred0 = pred_disp_l/s, up = pred_disp_l/(s+k) (the up-sampled coarse map), gt: n elements each.  One pass over gt:
+ * out4 = [khamis(pred0, gt), khamis(up, gt), out4[0] + out4[1] (fp32), max(count(gt > 0), 1)]; NaN in gt is not valid.
+ * workspace: as_khamis2_workspace(n) floats, 8-byte aligned.  Deterministic (fixed-order fp64 sums).
+ * as_khamis2_bwd: g_out3 = device gradients of out4[0..2].  g_pred0 [B,1,H,W] = (g_out3[0] + g_out3[2]) / out4[3] * d value /
+ * d pred0; g_coarse [B,h,w] = gain * (bilinear up-sampling adjoint, align_corners=False) of (g_out3[1] + g_out3[2]) / out4[3] *
+ * d value / d up, the derivative map formed where the adjoint loads it.  gain is the forward's (2^k), not W / w.  Ratios W / w
+ * beyond the adjoint's span are refused as by as_upsample_bilinear_bwd. */
+int64_t as_khamis2_workspace(int64_t n);
+int as_khamis2_fwd(const float* pred0, const float* up, const float* gt, int64_t n, float* out4, float* workspace,
+                   void* stream);
+int as_khamis2_bwd(const float* pred0, const float* up, const float* gt, const float* g_out3, const float* out4,
+                   int B, int H, int W, int h, int w, float gain, float* g_pred0, float* g_coarse, void* stream);
 
 /* ---- dataset layer on the device ----------------------------------------------------
  * What datasets/stereo_dataset.py:49-96 and utils/dataset_utils.py:26-57 do per sample on the host (ToTensor,

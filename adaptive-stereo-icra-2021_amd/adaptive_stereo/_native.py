@@ -208,6 +208,11 @@ _SIGNATURES = {
   "as_adam_step": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_float, c_float, c_float, c_float, c_int, c_vp,
                            c_vp]),
   "as_adam_step_lr": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_float, c_float, c_float, c_int, c_vp, c_vp]),
+  "as_sumsq_clip_gated": (c_int, [c_vp, c_i64, c_float, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+  "as_adam_step_gated": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_float, c_vp, c_float, c_float, c_float, c_int, c_vp,
+                                 c_vp, c_vp]),
+  "as_adapt_gate": (c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.c_double, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
+  "as_reservoir_store": (c_int, [c_vp, c_vp, c_i64, c_vp, c_int, c_vp, c_vp, c_vp]),
   "as_khamis2_workspace": (c_i64, [c_i64]),
   "as_khamis2_fwd": (c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
   "as_khamis2_bwd": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_float, c_vp, c_vp, c_vp]),

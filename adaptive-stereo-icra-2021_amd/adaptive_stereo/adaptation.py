@@ -136,7 +136,12 @@ class FusedClipAdam(object):
     self.coef = torch.ones(1, dtype=torch.float32, device=dev)
     self.ws = torch.empty(nat.load().as_sumsq_workspace(arena.numel), dtype=torch.float32, device=dev)
 
-  def step(self, clip=True):
+  def step(self, clip=True, gate=None):
+    """``gate`` (a device int32 tensor of one element): the gated entry points — with *gate == 0 parameters, both moments and the
+    device-side step counter stay as they are.  Whether a gated step counted is known on the device only: ``step_count`` is
+    not advanced here, refresh_step_count() reads it back."""
+    if gate is not None:
+      return self._step_gated(clip, gate)
     a = self.arena
     self.step_count += 1
     # the device-side step counter must move before the first Adam launch reads it: it rides on the clip's finalize launch
@@ -160,6 +165,28 @@ class FusedClipAdam(object):
       nat.call("as_adam_step", nat.ptr(a.params[s:e]), nat.ptr(a.grads[s:e]), nat.ptr(self.exp_avg[s:e]),
                nat.ptr(self.exp_avg_sq[s:e]), e - s, nat.ptr(scale), self.lr, self.betas[0], self.betas[1],
                self.eps, self.step_count, nat.ptr(self.step_dev), nat.stream())
+
+  def _step_gated(self, clip, gate):
+    if not (torch.is_tensor(gate) and gate.is_cuda and gate.dtype == torch.int32 and gate.numel() == 1):
+      raise ValueError("FusedClipAdam.step: gate must be a device int32 tensor of one element")
+    a = self.arena
+    ride = bool(clip) and self.clip_group == 0
+    if not ride:
+      self.step_dev += gate.reshape(1).to(torch.float32)
+    for gi, (s, e) in enumerate(a.group_bounds):
+      scale = None
+      if clip and gi == self.clip_group:
+        nat.call("as_sumsq_clip_gated", nat.ptr(a.grads[s:e]), e - s, float(self.max_norm), nat.ptr(self.sumsq), nat.ptr(self.coef),
+                 nat.ptr(self.step_dev) if (ride and gi == 0) else None, nat.ptr(self.ws), nat.ptr(gate), nat.stream())
+        scale = self.coef
+      nat.call("as_adam_step_gated", nat.ptr(a.params[s:e]), nat.ptr(a.grads[s:e]), nat.ptr(self.exp_avg[s:e]),
+               nat.ptr(self.exp_avg_sq[s:e]), e - s, nat.ptr(scale), self.lr, nat.ptr(self.lr_dev), self.betas[0], self.betas[1],
+               self.eps, 0, nat.ptr(self.step_dev), nat.ptr(gate), nat.stream())
+
+  def refresh_step_count(self):
+    """step_count from the device-side counter (a host read-back: gated steps advance only that one)."""
+    self.step_count = int(round(float(self.step_dev)))
+    return self.step_count
 
   def grad_norm(self):
     """Pre-clip L2 norm of the clipped group at the last step (device scalar)."""
@@ -491,8 +518,8 @@ class OnlineAdapter(object):
             "backprop_loss": backprop, "dp_terms": dp_terms, "fcs": fcs, "fcs_smoothed": self.fcs_smoothed,
             "outputs": out}
 
-  def backward_update(self, result):
-    """backward + clip + Adam for a result of forward_loss(train=True) (adapt.py:381-394).  Data parallel: every rank
+  def backward_update(self, result, gate=None):
+    """backward + clip + Adam for a result of forward_loss(train=True) (adapt.py:381-394).  ``gate``: FusedClipAdam.step's.  Data parallel: every rank
     back-propagates its local loss SUM (backward is linear in the incoming gradient), ONE all-reduce sums the gradient
     arena, and the division by the whole batch's valid-pixel count follows it — the same whole-batch masked mean that
     step() implements (_distributed_backward), not a mean of per-rank means."""
@@ -515,7 +542,7 @@ class OnlineAdapter(object):
     if self.dp:
       self._all_reduce_gradients()                             # the same single message step() sends
       self.arena.grads.div_(n_total)
-    self.optimizer.step(clip=self.clip)
+    self.optimizer.step(clip=self.clip, gate=gate)
 
   @torch.no_grad()
   def validation_loss(self, left, right):

@@ -7,11 +7,18 @@ operators.  Differences in form: validation takes the loss function as a callabl
 the only place that reads a device scalar back (and only in the VS / VS+ER modes, which need the
 decision on the host to route the pair into the reservoir), and the per-step work is delegated to
 ``OnlineAdapter``.
+
+``AdaptationLoop(..., captured=True)`` takes the three per-step decisions (novel or not, which reservoir slot if any, update
+or not) on the device instead (csrc/adapt_gate.hip: as_adapt_gate, as_reservoir_store; the gated clip + Adam of csrc/optim.hip)
+and replays an IN_PROGRESS step of every mode as ONE hipGraph without a host read-back; the reservoir is a ``DeviceReservoir``.
+Validation and ``StateMachine.transition`` stay on the host, at the loop's sync points.
 """
+import random
 from enum import Enum
 
 import torch
 
+from . import _native as nat
 from .utils.stereo_reservoir import StereoReservoir
 
 MODES = ("NONSTOP", "VS", "ER", "VS+ER", "NONE")
@@ -75,6 +82,90 @@ class StateMachine(object):
     return self.current_state
 
 
+class _SlotView(object):
+  """``DeviceReservoir.buf``: entry i as StereoReservoir's [value, index, left, right] (views of the device buffers).  The index
+  is the one the slot was appended with: a replacement keeps it, as it keeps the reference's index set."""
+
+  def __init__(self, owner):
+    self._o = owner
+
+  def __len__(self):
+    return self._o.size()
+
+  def __getitem__(self, i):
+    o = self._o
+    n = len(self)
+    if not -n <= i < n:
+      raise IndexError("reservoir slot %d of %d" % (i, n))
+    i %= n
+    return [o.values[i], int(o.indices[i]), o.left[i], o.right[i]]
+
+
+class DeviceReservoir(object):
+  """StereoReservoir with its pairs, values and bookkeeping in device memory, filled by as_adapt_gate / as_reservoir_store
+  (see include/adaptive_stereo_hip.h for the exact semantics: those of StereoReservoir.add, with random.randint(1, offers)
+  drawn as 1 + min(int(u * offers), offers - 1) from one uniform double per step).
+
+  state   int64 [size, offers, adds, updates]        indices int32 [capacity]      values fp32 [capacity]
+  left / right  fp32 [capacity, B, C, H, W], allocated when the first batch shows its shape
+  out3    int32 [novel, slot, update] of the last step
+
+  size(), average_value(), update_value() and buf[i] are StereoReservoir's, so StateMachine.validate / transition work on it
+  unchanged; each of them except update_value reads the device (a host synchronisation)."""
+
+  def __init__(self, max_size, device="cuda"):
+    if max_size < 1:
+      raise ValueError("DeviceReservoir: capacity must be at least 1")
+    self.max_size = int(max_size)
+    dev = torch.device(device)
+    self.state = torch.zeros(4, dtype=torch.int64, device=dev)
+    self.indices = torch.zeros(self.max_size, dtype=torch.int32, device=dev)
+    self.values = torch.zeros(self.max_size, dtype=torch.float32, device=dev)
+    self.out3 = torch.zeros(3, dtype=torch.int32, device=dev)
+    self.left = self.right = None
+    self._offered = False          # no launch of the gate yet: the size is 0 without asking the device
+    self.buf = _SlotView(self)
+
+  def allocate(self, like):
+    if self.left is None:
+      self.left = torch.zeros((self.max_size,) + tuple(like.shape), dtype=torch.float32, device=self.state.device)
+      self.right = torch.zeros_like(self.left)
+    elif tuple(self.left.shape[1:]) != tuple(like.shape):
+      raise ValueError("DeviceReservoir: batches of %s, allocated for %s" % (tuple(like.shape), tuple(self.left.shape[1:])))
+
+  # -- the two launches of a step (enqueue only) ----------------------------------------------------
+  def gate(self, fcs_smoothed, loss, batch_idx, u, threshold, gate_enabled, adapting):
+    self._offered = True
+    nat.call("as_adapt_gate", nat.ptr(fcs_smoothed), nat.ptr(loss), nat.ptr(batch_idx), nat.ptr(u), float(threshold),
+             self.max_size, int(bool(gate_enabled)), int(bool(adapting)), nat.ptr(self.state), nat.ptr(self.indices),
+             nat.ptr(self.values), nat.ptr(self.out3), nat.stream())
+
+  def store(self, left, right):
+    nat.call("as_reservoir_store", nat.ptr(left), nat.ptr(right), left.numel(), nat.ptr(self.out3[1:2]), self.max_size,
+             nat.ptr(self.left), nat.ptr(self.right), nat.stream())
+
+  # -- StereoReservoir's interface ------------------------------------------------------------------
+  def counters(self):
+    """(size, offers, adds, updates) as python ints."""
+    return tuple(int(v) for v in self.state.cpu().tolist())
+
+  def size(self):
+    if not self._offered:
+      return 0
+    return int(self.state[0])
+
+  @property
+  def i(self):
+    return int(self.state[1])
+
+  def update_value(self, buf_index, new_value):
+    self.values[buf_index:buf_index + 1].fill_(float(new_value))
+
+  def average_value(self):
+    vals = self.values[:self.size()].cpu().tolist()
+    return sum(vals) / len(vals)
+
+
 class AdaptationLoop(object):
   """The body of the reference's ``for inputs in adapt_loader`` (adapt.py:290-396) around an OnlineAdapter.
 
@@ -83,12 +174,28 @@ class AdaptationLoop(object):
   val_improve_retries see StateMachine.transition
   ood_threshold       a pair is novel when the smoothed FCS is below it
   er_loss_weight      weight of the Khamis loss on the replayed training pair (ER modes)
-  """
+  captured            the gated step (below); off, the loop is the host-side one and its results are unchanged
+
+  captured=True.  An IN_PROGRESS step is forward_loss, as_adapt_gate, as_reservoir_store, backward_update with the gated
+  optimizer: the same call sequence as the host loop, always including backward, with the update withheld on the device when the
+  pair went into the reservoir.  The first such step runs eagerly (it creates the FCS EMA and records the step plan), the second
+  is captured, every later one replays the graph: inputs are copied into static buffers, ``batch_idx`` and the step's uniform
+  number ``u`` reach the device by fill_ (kernel arguments), and nothing is read back.  result["updated"] and
+  result["added_to_ovs"] are 0-d device tensors.  ``gradient_updates`` and ``optimizer.step_count`` are refreshed from the device
+  at the sync points: every ``ovs_validate_hz`` steps (before validation), in DONE-state steps, and by sync() — call it before
+  ``optimizer.state_dict()`` / save_models.  DONE-state steps stay eager: they run as_adapt_gate with adapting = 0 and read
+  ``novel`` back to restart the machine, as StateMachine.add_to_ovs does.
+  Random numbers: the VS modes draw one random.random() per gated step; the host loop draws random.randint only on an offer to a
+  full buffer.  Both sample the reference's distribution; from one seed the two loops follow different sequences.
+  In the ER modes the replay triple must be given on every step or on none (one graph).  Single GPU only."""
 
   def __init__(self, adapter, mode="NONSTOP", ovs_buffer_size=10, ovs_validate_hz=100, val_improve_retries=1,
-               ood_threshold=15.0, er_loss_weight=0.05):
+               ood_threshold=15.0, er_loss_weight=0.05, captured=False):
     if mode not in MODES:
       raise ValueError("adapt_mode must be one of %s" % (MODES,))
+    if captured and getattr(adapter, "dp", False):
+      raise NotImplementedError("AdaptationLoop(captured=True) is single-GPU: a data-parallel adapter decides the gate on "
+                                "all-reduced scalars, which the captured step does not do; use captured=False")
     self.adapter = adapter
     self.mode = mode
     self.ovs_validate_hz = ovs_validate_hz
@@ -99,12 +206,25 @@ class AdaptationLoop(object):
     self.state_machine = StateMachine(initial, ovs_buffer_size=ovs_buffer_size)
     self.step = 0
     self.gradient_updates = 0
+    self.captured = bool(captured)
+    if self.captured:
+      dev = adapter.arena.params.device
+      self.state_machine.ovs = DeviceReservoir(ovs_buffer_size, dev)
+      self._batch_idx = torch.zeros(1, dtype=torch.int32, device=dev)
+      self._u = torch.zeros(1, dtype=torch.float64, device=dev)
+      self._static = None            # (left, right, replay triple or None): the captured step's own input buffers
+      self._graph = None
+      self._graph_result = None
+      self._use_replay = None
+      self._adds_seen = 0
 
   def _validation_loss(self, left, right):
     return self.adapter.validation_loss(left, right)
 
   def process(self, left, right, batch_idx, replay=None):
     """One batch.  ``replay`` = (left, right, gt_disp) of a training-domain pair for the ER modes."""
+    if self.captured:
+      return self._process_captured(left, right, batch_idx, replay)
     sm = self.state_machine
     if (self.step % self.ovs_validate_hz == 0) and sm.ovs_buffer_size() > 0 and sm.state() == State.IN_PROGRESS:
       sm.validate(self._validation_loss)
@@ -129,4 +249,125 @@ class AdaptationLoop(object):
       updated = True
     self.step += 1
     result.update(state=sm.state(), added_to_ovs=did_add, updated=updated)
+    return result
+
+  # -- captured=True ---------------------------------------------------------------------------------------------------
+  def sync(self):
+    """Refreshes the host mirrors of what gated steps count on the device (a host synchronisation): gradient_updates,
+    optimizer.step_count, and whether the reservoir changed since the last transition."""
+    if not self.captured:
+      return
+    _, _, adds, updates = self.state_machine.ovs.counters()
+    if adds != self._adds_seen:
+      self._adds_seen = adds
+      self.state_machine.ovs_did_change = True
+    self.gradient_updates = updates
+    self.adapter.optimizer.refresh_step_count()
+
+  def graph_count(self):
+    return 0 if not self.captured or self._graph is None else 1
+
+  def _bind_inputs(self, left, right, replay):
+    if self._static is None:
+      pair = torch.cat([left, right])              # the two images halves of one buffer: the pair pass needs no copy
+      sl, sr = pair[:left.shape[0]], pair[left.shape[0]:]
+      srep = None
+      if replay is not None:
+        rpair = torch.cat([replay[0], replay[1]])
+        srep = (rpair[:replay[0].shape[0]], rpair[replay[0].shape[0]:], replay[2].clone())
+      self._static = (sl, sr, srep)
+      self.state_machine.ovs.allocate(sl)
+      return
+    sl, sr, srep = self._static
+    sl.copy_(left); sr.copy_(right)
+    if srep is not None:
+      for dst, src in zip(srep, replay):
+        dst.copy_(src)
+
+  def _gated_body(self, threshold, gate_enabled, adapting):
+    """forward_loss, gate, store, backward_update on the static inputs: what the graph holds."""
+    sl, sr, srep = self._static
+    ovs = self.state_machine.ovs
+    result = self.adapter.forward_loss(sl, sr, train=True, replay=srep, er_loss_weight=self.er_loss_weight)
+    ovs.gate(result["fcs_smoothed"], result["loss"], self._batch_idx, self._u, threshold, gate_enabled, adapting)
+    ovs.store(sl, sr)
+    self.adapter.backward_update(result, gate=ovs.out3[2:3])
+    result["updated"] = ovs.out3[2]
+    result["added_to_ovs"] = ovs.out3[1] >= 0
+    result["novel"] = ovs.out3[0]
+    return result
+
+  def _capture(self, gate_enabled):
+    """Warm-up on the capture stream with the gate shut (nothing is novel, nothing adapts: the reservoir, the parameters, both
+    moments and the step count stay as they are), then the capture.  What a forward pass in train mode changes on its own — the
+    BatchNorm running statistics and counters, the FCS EMA — is put back afterwards, so the loop's state is the one it had."""
+    a = self.adapter
+    a._refuse_nested_capture("AdaptationLoop capture")
+    bufs = [b for net in (a.stereo_net, a.feature_net) for b in net.buffers()]
+    saved = [b.clone() for b in bufs]
+    ema = a.fcs_smoothed.clone()
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+      for _ in range(2):
+        self._gated_body(float("-inf"), False, False)
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    a._capture_origin = side.cuda_stream
+    try:
+      with torch.cuda.graph(graph, stream=side, capture_error_mode="thread_local"):
+        self._graph_result = self._gated_body(self.ood_threshold, gate_enabled, True)
+    finally:
+      a._capture_origin = None
+    with torch.no_grad():
+      for b, v in zip(bufs, saved):
+        b.copy_(v)
+      a.fcs_smoothed.copy_(ema)
+    self._graph = graph
+
+  def _process_captured(self, left, right, batch_idx, replay):
+    sm = self.state_machine
+    if self.step % self.ovs_validate_hz == 0 and sm.state() == State.IN_PROGRESS:
+      self.sync()
+      if sm.ovs_buffer_size() > 0:
+        sm.validate(self._validation_loss)
+        if self.mode not in ("NONSTOP", "ER", "NONE"):
+          sm.transition(self.val_improve_retries)
+
+    adapting = sm.state() == State.IN_PROGRESS
+    use_replay = self.mode in ("ER", "VS+ER") and replay is not None
+    gate = self.mode not in ("NONSTOP", "ER", "NONE")
+    if self._use_replay is None:
+      self._use_replay = use_replay
+    elif adapting and use_replay != self._use_replay:
+      raise ValueError("AdaptationLoop(captured=True): the replay triple must be given on every step or on none")
+    self._batch_idx.fill_(int(batch_idx))
+    if gate:
+      self._u.fill_(random.random())
+    if adapting:
+      self._bind_inputs(left, right, replay if use_replay else None)
+      if self._graph is None and self.adapter.fcs_smoothed is not None and self.adapter.plan.ready:
+        self._capture(gate)
+      if self._graph is not None:
+        self._graph.replay()
+        result = dict(self._graph_result)
+      else:
+        result = self._gated_body(self.ood_threshold, gate, True)
+    else:
+      # DONE: eval-mode forward without gradients, the gate with adapting = 0, and the one read-back that can restart the machine
+      ovs = sm.ovs
+      ovs.allocate(left)
+      result = self.adapter.forward_loss(left, right, train=False, replay=replay if use_replay else None,
+                                         er_loss_weight=self.er_loss_weight)      # (the replay loss is still reported, as by the host loop)
+      ovs.gate(result["fcs_smoothed"], result["loss"], self._batch_idx, self._u, self.ood_threshold, gate, False)
+      ovs.store(left.contiguous(), right.contiguous())
+      result["updated"] = ovs.out3[2].clone()
+      result["added_to_ovs"] = ovs.out3[1] >= 0
+      result["novel"] = ovs.out3[0].clone()
+      if gate and int(ovs.out3[0]) != 0:
+        sm.restart()
+      self.sync()
+    self.step += 1
+    result["state"] = sm.state()
     return result

@@ -93,15 +93,18 @@ __global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ g,
 }
 // (optionally also the clip coefficient of torch.nn.utils.clip_grad_norm_ and the optimizer's device-side step counter: three
 // one-thread jobs in the launch that exists anyway)
+// GATED: the step counter moves only where *gate != 0 (a step whose update the adaptation gate withholds keeps its count); out
+// and coef are written either way.
+template <bool GATED>
 __global__ void sumsq_finalize_kernel(const double* __restrict__ partial, int nblk, float* __restrict__ out, float max_norm,
-                                      float* __restrict__ coef, float* __restrict__ step_counter) {
+                                      float* __restrict__ coef, float* __restrict__ step_counter, const int32_t* __restrict__ gate) {
   double s = 0.0;                                // one wave; lane-strided, then a shuffle tree: fixed order
   for (int i = threadIdx.x; i < nblk; i += 64) s += partial[i];
   s = wave_sum_d(s);
   if (threadIdx.x == 0) {
     out[0] = (float)s;
     if (coef) coef[0] = fminf(max_norm / (sqrtf((float)s) + 1e-6f), 1.0f);      // as clip_coef_kernel, from the stored fp32 value
-    if (step_counter) step_counter[0] += 1.0f;
+    if (step_counter && (!GATED || gate[0] != 0)) step_counter[0] += 1.0f;
   }
 }
 
@@ -168,8 +171,8 @@ extern "C" int as_sumsq(const float* g, int64_t n, float* out, float* workspace,
   double* partial = reinterpret_cast<double*>(workspace);
   hipLaunchKernelGGL(sumsq_kernel, dim3((int)nb), dim3(256), 0, (hipStream_t)stream, g, (long)n, partial);
   AS_CHECK_LAUNCH("as_sumsq");
-  hipLaunchKernelGGL(sumsq_finalize_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, partial, (int)nb, out, 0.f,
-                     (float*)nullptr, (float*)nullptr);
+  hipLaunchKernelGGL(sumsq_finalize_kernel<false>, dim3(1), dim3(64), 0, (hipStream_t)stream, partial, (int)nb, out, 0.f,
+                     (float*)nullptr, (float*)nullptr, (const int32_t*)nullptr);
   AS_CHECK_LAUNCH("as_sumsq(finalize)");
   return AS_OK;
 }
@@ -183,9 +186,24 @@ extern "C" int as_sumsq_clip(const float* g, int64_t n, float max_norm, float* o
   double* partial = reinterpret_cast<double*>(workspace);
   hipLaunchKernelGGL(sumsq_kernel, dim3((int)nb), dim3(256), 0, (hipStream_t)stream, g, (long)n, partial);
   AS_CHECK_LAUNCH("as_sumsq_clip");
-  hipLaunchKernelGGL(sumsq_finalize_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, partial, (int)nb, out, max_norm, coef,
-                     step_counter);
+  hipLaunchKernelGGL(sumsq_finalize_kernel<false>, dim3(1), dim3(64), 0, (hipStream_t)stream, partial, (int)nb, out, max_norm, coef,
+                     step_counter, (const int32_t*)nullptr);
   AS_CHECK_LAUNCH("as_sumsq_clip(finalize)");
+  return AS_OK;
+}
+
+extern "C" int as_sumsq_clip_gated(const float* g, int64_t n, float max_norm, float* out, float* coef, float* step_counter,
+                                   float* workspace, const int32_t* gate, void* stream) {
+  AS_CHECK_ARG(g && out && coef && workspace && gate && n > 0 && max_norm > 0.f, "as_sumsq_clip_gated: bad argument");
+  AS_CHECK_ARG(((uintptr_t)workspace & 7) == 0, "as_sumsq_clip_gated: workspace must be 8-byte aligned");
+  long nb = (n + 255) / 256;
+  if (nb > SS_BLOCKS) nb = SS_BLOCKS;
+  double* partial = reinterpret_cast<double*>(workspace);
+  hipLaunchKernelGGL(sumsq_kernel, dim3((int)nb), dim3(256), 0, (hipStream_t)stream, g, (long)n, partial);
+  AS_CHECK_LAUNCH("as_sumsq_clip_gated");
+  hipLaunchKernelGGL(sumsq_finalize_kernel<true>, dim3(1), dim3(64), 0, (hipStream_t)stream, partial, (int)nb, out, max_norm, coef,
+                     step_counter, gate);
+  AS_CHECK_LAUNCH("as_sumsq_clip_gated(finalize)");
   return AS_OK;
 }
 
@@ -198,12 +216,15 @@ __device__ inline float clipped_grad(float g, float gs) {
   return g * gs;
 }
 // LR_DEV: the learning rate is *lr_dev (a device float: a captured step follows a schedule without a new capture), else lr.
-template <bool LR_DEV>
+// GATED: every workgroup returns before its first access when *gate == 0 (parameters and both moments untouched).
+template <bool LR_DEV, bool GATED = false>
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                     float* __restrict__ m, float* __restrict__ v, long n,
                                                     const float* __restrict__ grad_scale, float lr, const float* __restrict__ lr_dev,
                                                     float b1, float b2,
-                                                    float eps, int step_host, const float* __restrict__ step_dev) {
+                                                    float eps, int step_host, const float* __restrict__ step_dev,
+                                                    const int32_t* __restrict__ gate) {
+  if (GATED && gate[0] == 0) return;
   if (LR_DEV) lr = lr_dev[0];
   // bias corrections from the step count: a host integer, or (hipGraph replay) a device counter
   const double step = step_dev ? (double)step_dev[0] : (double)step_host;
@@ -228,7 +249,7 @@ extern "C" int as_adam_step(float* param, const float* grad, float* exp_avg, flo
   long nb = (n + 255) / 256;
   if (nb > 2048) nb = 2048;
   hipLaunchKernelGGL(adam_kernel<false>, dim3((int)nb), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq,
-                     (long)n, grad_scale_dev, lr, (const float*)nullptr, beta1, beta2, eps, step, step_dev);
+                     (long)n, grad_scale_dev, lr, (const float*)nullptr, beta1, beta2, eps, step, step_dev, (const int32_t*)nullptr);
   AS_CHECK_LAUNCH("as_adam_step");
   return AS_OK;
 }
@@ -240,7 +261,23 @@ extern "C" int as_adam_step_lr(float* param, const float* grad, float* exp_avg, 
   long nb = (n + 255) / 256;
   if (nb > 2048) nb = 2048;
   hipLaunchKernelGGL(adam_kernel<true>, dim3((int)nb), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq,
-                     (long)n, grad_scale_dev, 0.f, lr_dev, beta1, beta2, eps, step, step_dev);
+                     (long)n, grad_scale_dev, 0.f, lr_dev, beta1, beta2, eps, step, step_dev, (const int32_t*)nullptr);
   AS_CHECK_LAUNCH("as_adam_step_lr");
+  return AS_OK;
+}
+
+extern "C" int as_adam_step_gated(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
+                                  const float* grad_scale_dev, float lr, const float* lr_dev, float beta1, float beta2, float eps,
+                                  int step, const float* step_dev, const int32_t* gate, void* stream) {
+  AS_CHECK_ARG(param && grad && exp_avg && exp_avg_sq && gate && n > 0 && (step >= 1 || step_dev), "as_adam_step_gated: bad argument");
+  long nb = (n + 255) / 256;
+  if (nb > 2048) nb = 2048;
+  if (lr_dev)
+    hipLaunchKernelGGL((adam_kernel<true, true>), dim3((int)nb), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq,
+                       (long)n, grad_scale_dev, 0.f, lr_dev, beta1, beta2, eps, step, step_dev, gate);
+  else
+    hipLaunchKernelGGL((adam_kernel<false, true>), dim3((int)nb), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq,
+                       (long)n, grad_scale_dev, lr, (const float*)nullptr, beta1, beta2, eps, step, step_dev, gate);
+  AS_CHECK_LAUNCH("as_adam_step_gated");
   return AS_OK;
 }

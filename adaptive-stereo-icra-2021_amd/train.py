@@ -70,6 +70,8 @@ class TrainOptions(object):
     p.add_argument("--train_split", type=str)
     p.add_argument("--ood_threshold", type=float, default=15.0)
     p.add_argument("--fcs_ema_weight", type=float, default=0.999)
+    p.add_argument("--no_capture", action="store_true", default=False,
+                   help="adapt.py: the host-side adaptation loop instead of the captured, device-gated one")
     self.parser = p
 
   def parse(self, args=None):

@@ -648,6 +648,31 @@ int as_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg
 int as_adam_step_lr(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
                     const float* grad_scale_dev, const float* lr_dev, float beta1, float beta2, float eps,
                     int step, const float* step_dev, void* stream);
+/* The two above behind a device flag (`gate`, one int32): with *gate != 0 bit for bit as_sumsq_clip and as_adam_step (lr_dev
+ * NULL) / as_adam_step_lr (lr_dev given); with *gate == 0 the parameters, both moments and the step counter stay untouched,
+ * out and coef are still written.  An early return, never a wait. */
+int as_sumsq_clip_gated(const float* g, int64_t n, float max_norm, float* out, float* coef, float* step_counter,
+                        float* workspace, const int32_t* gate, void* stream);
+int as_adam_step_gated(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
+                       const float* grad_scale_dev, float lr, const float* lr_dev, float beta1, float beta2, float eps,
+                       int step, const float* step_dev, const int32_t* gate, void* stream);
+
+/* ---- validated adaptation on the device — adapt.py:366-396, utils/stereo_reservoir.py ------------
+ * as_adapt_gate: the three decisions of a step, by one wave.  Device inputs: fcs_smoothed, loss (fp32), batch_idx (int32),
+ * u (fp64 in [0,1): the step's random number).  state = [size, offers, adds, updates] (int64), indices[capacity] (int32),
+ * values[capacity] (fp32) persist; out3 = [novel, slot, update] (int32) is the step's output.
+ *   novel = gate_enabled && (double)fcs_smoothed < threshold                  (strict: a NaN is never novel)
+ *   novel: offers += 1; unless batch_idx is in indices[0:size]: size < capacity appends (slot = size, indices[size] =
+ *          batch_idx, size += 1), else r = 1 + min((int64)(u * offers), offers - 1) and slot = r - 1 when r <= capacity (a
+ *          replacement changes neither indices nor size, as the reference's reservoir); a slot: values[slot] = loss, adds += 1
+ *   update = adapting && slot < 0; updates += update
+ * as_reservoir_store: left and right (n floats each) into row *slot_dev of buf_left / buf_right ([capacity][n]); no write
+ * at all when the slot is < 0 or >= capacity.  16-byte accesses where both sides are 16-byte aligned. */
+int as_adapt_gate(const float* fcs_smoothed, const float* loss, const int32_t* batch_idx, const double* u,
+                  double threshold, int capacity, int gate_enabled, int adapting, int64_t* state,
+                  int32_t* indices, float* values, int32_t* out3, void* stream);
+int as_reservoir_store(const float* left, const float* right, int64_t n, const int32_t* slot_dev, int capacity,
+                       float* buf_left, float* buf_right, void* stream);
 
 /* ---- supervised two-scale loss — train.py:215, utils/loss_functions.py:18-38 with scales = [s, s + k] ----------
  * pred0 = pred_disp_l/s, up = pred_disp_l/(s+k) (the up-sampled coarse map), gt: n elements each.  One pass over gt:

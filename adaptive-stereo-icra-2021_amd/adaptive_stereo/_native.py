@@ -125,6 +125,10 @@ _SIGNATURES = {
   "as_conv3d_wgrad_lds_assignment": (c_int, [c_int, c_int, c_int, c_vp, c_vp, c_vp]),
   "as_conv32_s2_enable": (c_int, [c_int]),
   "as_conv4_s2_enable": (c_int, [c_int]),
+  "as_conv4_s2_ok": (c_int, [_P(Pcl), _P(Pcl), _P(ConvShape)]),
+  "as_conv32_s2_fwd_ok": (c_int, [_P(Pcl), _P(Pcl), _P(ConvShape)]),
+  "as_conv32_s2_dgrad_ok": (c_int, [_P(Pcl), _P(Pcl)]),
+  "as_conv32_wgrad_segments": (c_int, [_P(Pcl), _P(Pcl), _P(ConvShape)]),
   "as_refine_out_ok": (c_int, [_P(Pcl)]),
   "as_refine_out_fwd": (c_int, [c_vp, c_vp, c_vp, c_vp, c_float, c_vp, _P(Pcl), c_vp, c_vp, c_vp, c_int, c_vp, c_vp]),
   "as_conv32_bwd_fused_ok": (c_int, [_P(Pcl), _P(Pcl), _P(ConvShape)]),

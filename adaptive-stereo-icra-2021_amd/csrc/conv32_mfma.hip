@@ -680,6 +680,15 @@ extern "C" int as_conv32_dgrad_s2(const float* gz, const as_pcl* ggz, const floa
   return as_conv32_dgrad_s2_packed(gz, ggz, workspace, gx, ggx, stream);
 }
 
+// Whether as_conv32_dgrad_s2_packed launches conv32_s2_dgrad_kernel (the entry point's own test, switch included).
+static bool conv32_s2_dgrad_takes(const as_pcl* ggz, const as_pcl* ggx) {
+  return g_conv32_s2 && conv32_s2_dgrad_applicable(ggz, ggx);
+}
+extern "C" int as_conv32_s2_dgrad_ok(const as_pcl* ggz, const as_pcl* ggx) {
+  if (!as_pcl_ok(ggz) || !as_pcl_ok(ggx)) return AS_ERR_ARG;
+  return conv32_s2_dgrad_takes(ggz, ggx) ? 1 : 0;
+}
+
 extern "C" int as_conv32_dgrad_s2_packed(const float* gz, const as_pcl* ggz, const float* packed, float* gx, const as_pcl* ggx,
                                          void* stream) {
   const float* w = packed; float* workspace = const_cast<float*>(packed);
@@ -689,7 +698,7 @@ extern "C" int as_conv32_dgrad_s2_packed(const float* gz, const as_pcl* ggz, con
                "as_conv32_dgrad_s2: gz extent is not that of a 5x5 stride-2 pad-2 convolution of gx's extent");
   AS_CHECK_ARG(ggz->ph >= 1 && ggz->pw >= 1, "as_conv32_dgrad_s2: gz needs a zero halo of 1");
   hipStream_t st = (hipStream_t)stream;
-  if (g_conv32_s2 && conv32_s2_dgrad_applicable(ggz, ggx)) {
+  if (conv32_s2_dgrad_takes(ggz, ggx)) {
     as_prof_mark(AS_PROF_CONV32, st, 1, 0.0);
     if (int e = conv32_s2_dgrad_launch(gz, ggz, packed, gx, ggx, stream)) return e;
     as_prof_mark(AS_PROF_CONV32, st, 0, 2.0 * (double)ggx->B * ggz->H * ggz->W * 1024.0 * 25.0);
@@ -1118,6 +1127,20 @@ extern "C" int as_conv32_stat_parts(const as_pcl* gin, const as_pcl* gout, const
   return as_conv32_num_blocks(gout);
 }
 
+// Whether as_conv32_fwd launches conv32_s2_fwd_kernel (the entry point's own test, switch included; as_conv32_s2_fwd_ok
+// answers it for epilogue 0 without residual and moments): no LDS kernel takes the layer, and split-K has precedence.
+static bool conv32_s2_fwd_takes(const as_pcl* gin, const as_pcl* gout, const as_conv_shape* s, int epilogue, bool residual,
+                                bool moments) {
+  if (conv32_lds_applicable(gin, gout, s) || conv3d_lds_applicable(gin, gout, s)) return false;
+  const int64_t M_all = (int64_t)gout->B * gout->D * gout->H * gout->W;
+  return epilogue == 0 && !residual && !moments && g_conv32_s2 && conv32_s2_fwd_applicable(gin, gout, s) &&
+         !conv32_splitk_applies(25, M_all);
+}
+extern "C" int as_conv32_s2_fwd_ok(const as_pcl* gin, const as_pcl* gout, const as_conv_shape* s) {
+  if (check_conv(gin, gout, s, "as_conv32_s2_fwd_ok")) return AS_ERR_ARG;
+  return conv32_s2_fwd_takes(gin, gout, s, 0, false, false) ? 1 : 0;
+}
+
 extern "C" int as_conv32_fwd(const float* x, const as_pcl* gin, const float* packed_w, const float* bias,
                              float* z, const as_pcl* gout, const as_conv_shape* s,
                              int epilogue, const float* ep_scale, const float* ep_shift, float slope,
@@ -1132,8 +1155,7 @@ extern "C" int as_conv32_fwd(const float* x, const as_pcl* gin, const float* pac
     return conv3d_lds_launch(x, gin, packed_w, bias, z, gout, epilogue, ep_scale, ep_shift, slope, residual,
                              stat_mean, stat_m2, stat_cnt, stream);
   const int64_t M_all = (int64_t)gout->B * gout->D * gout->H * gout->W;
-  if (epilogue == 0 && residual == nullptr && stat_mean == nullptr && g_conv32_s2 && conv32_s2_fwd_applicable(gin, gout, s) &&
-      !conv32_splitk_applies(25, M_all)) {
+  if (conv32_s2_fwd_takes(gin, gout, s, epilogue, residual != nullptr, stat_mean != nullptr)) {
     // the strided head of the feature towers on maps that fill the chip: coalesced row staging (csrc/conv32_s2.hip)
     hipStream_t st2 = (hipStream_t)stream;
     as_prof_mark(0, st2, 1, 0.0);
@@ -1199,6 +1221,14 @@ static int wgrad_plan(const as_pcl* gout, const as_conv_shape* s, int* tg, int* 
 
 static bool wgrad_lds_applicable(const as_pcl* gin, const as_pcl* gout, const as_conv_shape* s) {
   return conv32_lds_applicable(gin, gout, s) && gout->pw >= 8;   // G groups beyond W read 8 zero halo voxels
+}
+
+// Segments per row of conv32_wgrad_kernel for this layer; 0 when an LDS kernel takes it (as as_conv32_wgrad decides).
+extern "C" int as_conv32_wgrad_segments(const as_pcl* gin, const as_pcl* gout, const as_conv_shape* s) {
+  if (check_conv(gin, gout, s, "as_conv32_wgrad_segments")) return AS_ERR_ARG;
+  if (wgrad_lds_applicable(gin, gout, s) || conv3d_wgrad_lds_applicable(gin, gout, s)) return 0;
+  int seg_steps;
+  return wgrad_segments(gout, s, &seg_steps);
 }
 
 extern "C" int64_t as_conv32_wgrad_workspace(const as_pcl* gin, const as_pcl* gout, const as_conv_shape* s) {

@@ -1000,6 +1000,16 @@ extern "C" int as_conv4_stat_parts(const as_pcl* gin, const as_pcl* gout, const 
   return as_div_up((int64_t)gout->B * gout->H * gout->W, 128);
 }
 
+// Whether as_conv4_fwd launches conv4_s2_fwd_kernel (the entry point's own test; as_conv4_s2_ok answers it for a plain epilogue
+// without moments).
+static bool conv4_s2_takes(const as_pcl* gin, const as_pcl* gout, const as_conv_shape* s, int epilogue, bool moments) {
+  return !conv4_rows_applicable(gin, gout, s) && g_conv4_s2 && epilogue == 0 && !moments && conv4_s2_applicable(gin, gout, s);
+}
+extern "C" int as_conv4_s2_ok(const as_pcl* gin, const as_pcl* gout, const as_conv_shape* s) {
+  if (check4(gin, gout, s, "as_conv4_s2_ok")) return AS_ERR_ARG;
+  return conv4_s2_takes(gin, gout, s, 0, false) ? 1 : 0;
+}
+
 extern "C" int as_conv4_fwd(const float* x4, const as_pcl* gin, const float* packed_w, const float* bias,
                             float* z, const as_pcl* gout, const as_conv_shape* s,
                             int epilogue, const float* ep_scale, const float* ep_shift, float slope,
@@ -1025,7 +1035,7 @@ extern "C" int as_conv4_fwd(const float* x4, const as_pcl* gin, const float* pac
     AS_CHECK_LAUNCH("as_conv4_fwd(rows)");
     return AS_OK;
   }
-  if (g_conv4_s2 && epilogue == 0 && !stat_mean && conv4_s2_applicable(gin, gout, s)) {
+  if (conv4_s2_takes(gin, gout, s, epilogue, stat_mean != nullptr)) {
     Conv4S2Args q;
     q.x4 = x4; q.wp = packed_w; q.bias = bias; q.z = z; q.gin = as_make_dev(gin); q.gout = as_make_dev(gout);
     q.nseg = (gout->W + 31) / 32; q.ntiles = gout->B * gout->H * q.nseg;

@@ -222,6 +222,17 @@ int as_conv32_s2_enable(int on);
  * it on conv4_s2_fwd_kernel (persistent waves, rows staged through wave-private LDS) when the epilogue is plain and the map fills
  * the chip; bit-identical to conv4_fwd_kernel<25> */
 int as_conv4_s2_enable(int on);
+/* Read-only route queries: what the entry points would launch NOW for this geometry, switch included (the routes give equal bits
+ * by design, so only a query can tell a test which kernel ran).  1 / 0, or AS_ERR_ARG where the entry point would refuse.
+ *   as_conv4_s2_ok          as_conv4_fwd with a plain epilogue (0) and no moments launches conv4_s2_fwd_kernel
+ *   as_conv32_s2_fwd_ok     as_conv32_fwd with epilogue 0, no residual and no moments launches conv32_s2_fwd_kernel (switch on,
+ *                           the map fills the chip, and split-K does not take precedence)
+ *   as_conv32_s2_dgrad_ok   as_conv32_dgrad_s2_packed launches conv32_s2_dgrad_kernel
+ *   as_conv32_wgrad_segments  segments per row of as_conv32_wgrad's generic kernel (>= 1), 0 when an LDS kernel takes the layer */
+int as_conv4_s2_ok(const as_pcl* gin, const as_pcl* gout, const as_conv_shape* s);
+int as_conv32_s2_fwd_ok(const as_pcl* gin, const as_pcl* gout, const as_conv_shape* s);
+int as_conv32_s2_dgrad_ok(const as_pcl* ggz, const as_pcl* ggx);
+int as_conv32_wgrad_segments(const as_pcl* gin, const as_pcl* gout, const as_conv_shape* s);
 
 /* ---- the refinement's output layer with the last BasicBlock's activation on the way in (csrc/refine_out.hip;
  * stereo_net.py:44-51, 102, 116-121):  out = relu?(conv2d_out(a) + bias + add_src)  where

@@ -437,18 +437,21 @@ def test_sumsq_and_adam_step():
 
 
 # ----------------------------------------------------------------------------- thin-input conv (Cin <= 4)
-@pytest.mark.parametrize("B,H,W", [(8, 375, 1242), (2, 540, 960), (3, 301, 515)])
+@pytest.mark.parametrize("B,H,W", [(8, 375, 1242), (2, 540, 960), (3, 301, 515), (4, 301, 515)])
 def test_first_head_layer_on_staged_rows_equals_the_one_tile_kernel(B, H, W):
   """downsample[0] = Conv2d(3, 32, 5, stride=2, padding=2) (stereo_net.py:61-69) on conv4_s2_fwd_kernel (persistent waves,
   rows staged through wave-private LDS) and its weight gradient on conv4_s2_wgrad_kernel (input rows staged in LDS) against
   conv4_fwd_kernel<25> / conv4_wgrad_kernel<4> (as_conv4_s2_enable(0)): the forward bit for bit — taps and channels in the same
   order —, nothing written into the output's halo; the weight gradient (the same products in differently cut chunks) to 2e-5 of
   its largest entry; everything against torch on the CPU.  The bench workload (8 images of 375 x 1242),
-  SceneFlow size, odd extents with a ragged last segment (W_out = 258 = 8 x 32 + 2)."""
+  SceneFlow size, and odd extents with a ragged last segment (W_out = 258 = 8 x 32 + 2) at 4 images (5436 tiles).  The same
+  extents at 3 images are 4077 tiles, below the 4096 the staged forward kernel starts at: there both settings run
+  conv4_fwd_kernel<25> (the route is asserted through as_conv4_s2_ok) and only the two weight-gradient kernels differ."""
   shape = ConvShape(1, 5, 5, 0, 2, 2, 1, 2)
   Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
   g4, gout = Pcl(B, 1, H, W, 0, 2, 2), Pcl(B, 1, Ho, Wo, 0, 2, 2)
   lib = nat.load()
+  staged = 0 if (B, H, W) == (3, 301, 515) else 1
   x = rnd(B, 3, H, W, seed=1); w = rnd(32, 3, 5, 5, seed=2, scale=0.115); b = rnd(32, seed=3, scale=0.1)
   x4 = torch.zeros(lib.as_pcl4_numel(g4), device=DEV)
   nat.call("as_pack_in4", None, nat.ptr(x.to(DEV)), 3, nat.ptr(x4), g4, nat.stream())
@@ -462,6 +465,7 @@ def test_first_head_layer_on_staged_rows_equals_the_one_tile_kernel(B, H, W):
   try:
     for on in (0, 1):
       lib.as_conv4_s2_enable(on)
+      assert lib.as_conv4_s2_ok(g4, gout, shape) == (staged if on else 0)
       z = ops.pcl_zeros(gout, DEV)
       nat.call("as_conv4_fwd", nat.ptr(x4), g4, nat.ptr(wp), nat.ptr(bd), nat.ptr(z), gout, shape, 0, None, None, 0.2,
                None, None, None, nat.stream())
@@ -695,6 +699,9 @@ def test_strided_head_on_staged_rows_equals_the_generic_kernels(B, H, W):
   try:
     for on in (0, 1):
       lib.as_conv32_s2_enable(on)
+      # (40 images of 21 x 33 are 440 tiles: split-K forward and the generic four-phase data gradient in both settings)
+      staged = 0 if (B, H, W) == (40, 21, 33) else on
+      assert lib.as_conv32_s2_fwd_ok(gin, gout, shape) == staged and lib.as_conv32_s2_dgrad_ok(gout, gin) == staged
       z = ops.conv32(xb, gin, wp, bd, gout, shape, out=ops.pcl_zeros(gout, DEV))
       gx = ops.pcl_zeros(gin, DEV)
       nat.call("as_conv32_dgrad_s2", nat.ptr(gzb), gout, nat.ptr(wd), nat.ptr(gx), gin, nat.ptr(ws), nat.stream())

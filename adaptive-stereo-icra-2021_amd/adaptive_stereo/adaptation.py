@@ -28,11 +28,9 @@ import torch.distributed as dist
 
 from . import _native as nat
 from . import hip_ops
-from .hip_ops import masked_mean, MaskedMeanFn
+from .capture import capture_graph, copy_unless_same, refuse_nested, static_pair, warm_up, warm_up_and_capture
 from .models.linear_warping import LinearWarping
-from .utils.loss_functions import monodepth_loss
 from .utils.feature_contrast import feature_contrast_mean
-from .utils.ema import online_ema
 
 
 def _release_comm(comm):
@@ -312,10 +310,8 @@ class OnlineAdapter(object):
   @torch.no_grad()
   def infer(self, left, right):
     if self._infer_graph is not None:
-      if left.data_ptr() != self._infer_left.data_ptr():
-        self._infer_left.copy_(left)
-      if right.data_ptr() != self._infer_right.data_ptr():
-        self._infer_right.copy_(right)
+      copy_unless_same(self._infer_left, left)
+      copy_unless_same(self._infer_right, right)
       self._infer_graph.replay()
       return self._infer_result
     return self._infer_eager(left, right)
@@ -372,24 +368,11 @@ class OnlineAdapter(object):
   def capture_infer(self, left, right, warmup=2):
     """Captures the eval-mode forward (~75 launches) into a hipGraph; infer() replays it from then on.  The graph
     reads the weights where they live (the flat arena), so it stays valid across adaptation steps."""
-    self._refuse_nested_capture("capture_infer")
-    pair = torch.cat([left, right])                      # one buffer: the two images are its halves, so the batched
-    self._infer_left, self._infer_right = pair[:left.shape[0]], pair[left.shape[0]:]   # feature pass needs no copy
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-      for _ in range(max(2, warmup)):          # the first call records the plan, the second runs it
-        self._infer_eager(self._infer_left, self._infer_right)
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    self._capture_origin = side.cuda_stream
-    try:
-      with torch.cuda.graph(graph, stream=side, capture_error_mode="thread_local"):   # same stream as the warm-up: the
-        self._infer_result = self._infer_eager(self._infer_left, self._infer_right)     # buffer pool is per stream
-    finally:
-      self._capture_origin = None
-    self._infer_graph = graph
+    refuse_nested("OnlineAdapter.capture_infer")
+    self._infer_left, self._infer_right = static_pair(left, right)
+    forward = lambda: self._infer_eager(self._infer_left, self._infer_right)
+    # (warm-up: the first call records the plan, the second runs it)
+    self._infer_graph, self._infer_result = warm_up_and_capture(forward, max(2, warmup), forward, owner=self)
     return self
 
   # -- one adaptation step: adapt.py:304-396 (NONSTOP) --------------------------------------------
@@ -417,10 +400,8 @@ class OnlineAdapter(object):
     self.feature_net.train(); self.stereo_net.train()
     self.arena.rebind_grads()
     self.arena.zero_grads()
-    self.plan.begin()
-    prev_sync = hip_ops.set_bn_sync(self.bn_sync)
-    hip_ops.rmw_order_reset(True)        # two streams update the same gradient sinks / running statistics: keep order
-    try:
+    # (multi-stream: two streams update the same gradient sinks / running statistics: keep order)
+    with hip_ops.step_region(self.plan, self.bn_sync):
       (loss, lsum, count), fcs_map, out, warped = self._forward_maps(left, right)
 
       if not self.dp:
@@ -428,19 +409,18 @@ class OnlineAdapter(object):
         loss.backward()
       else:
         loss, fcs = self._distributed_backward(lsum, count, fcs_map)
-    finally:
-      hip_ops.rmw_order_reset(False)
-      hip_ops.set_bn_sync(prev_sync)
-      self.plan.end()
 
     self.optimizer.step(clip=self.clip)
-    # FCS EMA (adapt.py:356-359), in place so that a captured graph keeps updating the same tensor
+    self._update_fcs_ema(fcs)
+    out["left_warped/{}".format(self.scale)] = warped
+    return {"loss": loss.detach(), "fcs": fcs, "fcs_smoothed": self.fcs_smoothed, "outputs": out}
+
+  def _update_fcs_ema(self, fcs):
+    """FCS EMA (adapt.py:356-359): created on first use, then in place so that a captured graph keeps updating the same tensor."""
     if self.fcs_smoothed is None:
       self.fcs_smoothed = fcs.detach().clone()
     else:
       self.fcs_smoothed.mul_(self.fcs_ema_weight).add_(fcs.detach(), alpha=1.0 - self.fcs_ema_weight)
-    out["left_warped/{}".format(self.scale)] = warped
-    return {"loss": loss.detach(), "fcs": fcs, "fcs_smoothed": self.fcs_smoothed, "outputs": out}
 
   # -- split step for the control plane (control.AdaptationLoop): the OOD gate sits between forward and backward
   def forward_loss(self, left, right, train=True, replay=None, er_loss_weight=0.05):
@@ -457,33 +437,25 @@ class OnlineAdapter(object):
     if train:
       self.arena.rebind_grads()
       self.arena.zero_grads()
-    if train:
-      self.plan.begin()
-    prev_sync = hip_ops.set_bn_sync(self.bn_sync if train else None)
     two_streams = self.bn_sync is None or not train
-    hip_ops.rmw_order_reset(two_streams)
-    try:
-      with torch.set_grad_enabled(train):
-        if not train:
-          fl, fr = self._features_eval(left, right)
-        else:
-          fl, fr = self._features_train(left, right) if two_streams else (self.feature_net(left), self.feature_net(right))
-        out = self.stereo_net(left, fl, fr, "l", output_cost_volume=True)
-        pred = out["pred_disp_l/{}".format(self.scale)]
-        loss, lsum, count, warped, _mask = hip_ops.MaskedPhotometricFn.apply(pred, left, right, self.sw)
-        backprop = loss
-        replay_loss = None
-        if replay is not None:
-          rl, rr, rgt = replay
-          rfl, rfr = self._features_train(rl, rr) if two_streams else (self.feature_net(rl), self.feature_net(rr))
-          rout = self.stereo_net(rl, rfl, rfr, "l", output_cost_volume=True)
-          replay_loss = khamis_robust_loss(rout["pred_disp_l/{}".format(self.scale)], rgt)
-          backprop = loss + er_loss_weight * replay_loss
-    finally:
-      hip_ops.rmw_order_reset(False)
-      hip_ops.set_bn_sync(prev_sync)
-      if train:
-        self.plan.end(final=False)
+    # train: the plan's forward section (backward_update resumes it); eval: no plan, no cross-replica BatchNorm
+    region = hip_ops.step_region(self.plan, self.bn_sync, two_streams, final=False) if train else hip_ops.step_region()
+    with region, torch.set_grad_enabled(train):
+      if not train:
+        fl, fr = self._features_eval(left, right)
+      else:
+        fl, fr = self._features_train(left, right) if two_streams else (self.feature_net(left), self.feature_net(right))
+      out = self.stereo_net(left, fl, fr, "l", output_cost_volume=True)
+      pred = out["pred_disp_l/{}".format(self.scale)]
+      loss, lsum, count, warped, _mask = hip_ops.MaskedPhotometricFn.apply(pred, left, right, self.sw)
+      backprop = loss
+      replay_loss = None
+      if replay is not None:
+        rl, rr, rgt = replay
+        rfl, rfr = self._features_train(rl, rr) if two_streams else (self.feature_net(rl), self.feature_net(rr))
+        rout = self.stereo_net(rl, rfl, rfr, "l", output_cost_volume=True)
+        replay_loss = khamis_robust_loss(rout["pred_disp_l/{}".format(self.scale)], rgt)
+        backprop = loss + er_loss_weight * replay_loss
     fcs_map = feature_contrast_mean(out["cost_volume_l/{}".format(self.coarse_scale)])
     fcs = fcs_map.mean()
     dp_terms = None
@@ -509,10 +481,7 @@ class OnlineAdapter(object):
         replay_loss = replay_whole
       else:
         dp_terms = (lsum, None, None, six[0])
-    if self.fcs_smoothed is None:
-      self.fcs_smoothed = fcs.detach().clone()
-    else:
-      self.fcs_smoothed.mul_(self.fcs_ema_weight).add_(fcs.detach(), alpha=1.0 - self.fcs_ema_weight)
+    self._update_fcs_ema(fcs)
     out["left_warped/{}".format(self.scale)] = warped
     return {"loss": loss.detach(), "replay_loss": None if replay_loss is None else replay_loss.detach(),
             "backprop_loss": backprop, "dp_terms": dp_terms, "fcs": fcs, "fcs_smoothed": self.fcs_smoothed,
@@ -523,10 +492,8 @@ class OnlineAdapter(object):
     back-propagates its local loss SUM (backward is linear in the incoming gradient), ONE all-reduce sums the gradient
     arena, and the division by the whole batch's valid-pixel count follows it — the same whole-batch masked mean that
     step() implements (_distributed_backward), not a mean of per-rank means."""
-    self.plan.begin(resume=True)  # backward re-packs the (unchanged) weights: one launch
-    prev_sync = hip_ops.set_bn_sync(self.bn_sync)
-    hip_ops.rmw_order_reset(self.bn_sync is None)
-    try:
+    # (resuming the plan re-packs the (unchanged) weights: one launch)
+    with hip_ops.step_region(self.plan, self.bn_sync, self.bn_sync is None, resume=True):
       if self.dp:
         lsum, replay_loss, replay_coef, n_total = result["dp_terms"]
         if replay_loss is None:
@@ -535,10 +502,6 @@ class OnlineAdapter(object):
           torch.autograd.backward([lsum, replay_loss], [torch.ones_like(lsum), replay_coef.reshape(replay_loss.shape)])
       else:
         result["backprop_loss"].backward()
-    finally:
-      hip_ops.rmw_order_reset(False)
-      hip_ops.set_bn_sync(prev_sync)
-      self.plan.end()
     if self.dp:
       self._all_reduce_gradients()                             # the same single message step() sends
       self.arena.grads.div_(n_total)
@@ -589,10 +552,9 @@ class OnlineAdapter(object):
   # -- hipGraph capture of the whole step ------------------------------------------------------------
   def capture(self, left, right, warmup=3):
     """Captures one adaptation step (forward, loss, backward, clip, Adam, EMA: ~130 kernel launches) into
-    hipGraphs and replays them from then on.  (capture_error_mode="thread_local": the process-group watchdog thread
-    queries events while a capture is open; only this thread's calls have to be capture-safe.)  Every entry point of the C ABI only enqueues work on the current
-    stream, so the capture sees them as plain kernel nodes; the Adam step count lives on the device.  Inputs
-    are copied into static buffers before each replay.
+    hipGraphs and replays them from then on (the capture rules: capture.py).  Every entry point of the C ABI only enqueues
+    work on the current stream, so the capture sees them as plain kernel nodes; the Adam step count lives on the device.
+    Inputs are copied into static buffers before each replay.  The warm-up steps are real adaptation steps.
     One GPU: a single graph.  Data parallel with this library's own RCCL communicator (self.comm): a single graph as
     well — the all-reduce (and, with sync_bn, the BatchNorm collectives) are graph nodes.  Data parallel over
     torch.distributed collectives (gloo, or no native communicator): two graphs (forward + backward of the local loss
@@ -601,71 +563,49 @@ class OnlineAdapter(object):
     if self.bn_sync is not None and self.comm is None:
       raise RuntimeError("OnlineAdapter.capture: cross-replica BatchNorm puts collectives inside forward and backward; "
                          "over torch.distributed collectives a step cannot be captured with sync_bn=True (step() runs eagerly)")
-    self._refuse_nested_capture("capture")
-    # one buffer, the two images its halves: the pair pass of the feature extractor then needs no concatenation copy
-    pair = torch.cat([left, right])
-    self._static_left, self._static_right = pair[:left.shape[0]], pair[left.shape[0]:]
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-      for _ in range(max(1, warmup)):
-        self._step_eager(self._static_left, self._static_right)
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    self.optimizer.step_count_at_capture = self.optimizer.step_count
-    self._capture_origin = side.cuda_stream
-    try:
-      self._capture_graphs(side)
-    finally:
-      self._capture_origin = None
-    # capture only records: the python-side counter advanced, the device-side one did not
-    self.optimizer.step_count = self.optimizer.step_count_at_capture
+    refuse_nested("OnlineAdapter.capture")
+    left, right = self._static_left, self._static_right = static_pair(left, right)
+    side = warm_up(lambda: self._step_eager(left, right), max(1, warmup))
+    step_count = self.optimizer.step_count
+    self._capture_graphs(side)
+    self.optimizer.step_count = step_count   # capture only records: the host counter advanced, the device-side one did not
     return self
-
-  def _refuse_nested_capture(self, what):
-    if torch.cuda.is_current_stream_capturing():
-      raise RuntimeError("OnlineAdapter.%s: the current stream is already being captured; a capture inside a capture "
-                         "(and the stream fork it implies) crashes hipStreamEndCapture on ROCm 7.2 — capture from an "
-                         "ordinary stream, or call step()/infer() inside your own capture (they then run the "
-                         "one-stream order)" % what)
 
   def _capture_graphs(self, side):
     left, right = self._static_left, self._static_right
     if not self.dp or self.comm is not None:
       if self.dp:
         dist.barrier(group=self.pg)
-      graph = torch.cuda.CUDAGraph()
-      with torch.cuda.graph(graph, stream=side, capture_error_mode="thread_local"):   # the warm-up's stream: its
-        self._static_result = self._step_eager(self._static_left, self._static_right)   # pooled buffers are reused
-      self._graph = graph
-    else:
-      if self.pg is not None or dist.is_initialized():
-        dist.barrier(group=self.pg)
-      cap = side                         # forward and backward are captured on the same stream (autograd replays
-      g1, g2 = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()              # backward where forward ran)
-      with torch.cuda.graph(g1, stream=cap, capture_error_mode="thread_local"):
-        self.feature_net.train(); self.stereo_net.train()
-        self.arena.rebind_grads()
-        self.arena.zero_grads()
-        self.plan.begin()
-        hip_ops.rmw_order_reset(True)
-        try:
-          (_, lsum, count), fcs_map, out, warped = self._forward_maps(self._static_left, self._static_right)
-          self._dp_local_sums(lsum, count, fcs_map)
-          self._dp_backward(lsum)
-        finally:
-          hip_ops.rmw_order_reset(False)
-          self.plan.end()
-      torch.cuda.synchronize()
-      allreduce_gradients_and_scalars(self.arena, self.pg)
-      torch.cuda.synchronize()
-      with torch.cuda.graph(g2, pool=g1.pool(), stream=cap, capture_error_mode="thread_local"):
-        loss, fcs = self._dp_results()
-        self.optimizer.step(clip=self.clip)
-        self.fcs_smoothed.mul_(self.fcs_ema_weight).add_(fcs.detach(), alpha=1.0 - self.fcs_ema_weight)
-        out["left_warped/{}".format(self.scale)] = warped
-        self._static_result = {"loss": loss.detach(), "fcs": fcs, "fcs_smoothed": self.fcs_smoothed, "outputs": out}
-      self._graph = (g1, g2)
+      self._graph, self._static_result = capture_graph(side, lambda: self._step_eager(left, right), owner=self)
+      return
+    if self.pg is not None or dist.is_initialized():
+      dist.barrier(group=self.pg)
+
+    def forward_backward():
+      self.feature_net.train(); self.stereo_net.train()
+      self.arena.rebind_grads()
+      self.arena.zero_grads()
+      # bn_sync=None changes nothing here: capture() has refused cross-replica BatchNorm over torch.distributed collectives
+      with hip_ops.step_region(self.plan, bn_sync=None):
+        (_, lsum, count), fcs_map, out, warped = self._forward_maps(left, right)
+        self._dp_local_sums(lsum, count, fcs_map)
+        self._dp_backward(lsum)
+      return out, warped
+
+    def update():
+      loss, fcs = self._dp_results()
+      self.optimizer.step(clip=self.clip)
+      self._update_fcs_ema(fcs)
+      out["left_warped/{}".format(self.scale)] = warped
+      return {"loss": loss.detach(), "fcs": fcs, "fcs_smoothed": self.fcs_smoothed, "outputs": out}
+
+    # both on the warm-up's stream: autograd replays backward where forward ran, and the second graph shares the first's pool
+    g1, (out, warped) = capture_graph(side, forward_backward, owner=self)
+    torch.cuda.synchronize()
+    allreduce_gradients_and_scalars(self.arena, self.pg)
+    torch.cuda.synchronize()
+    g2, self._static_result = capture_graph(side, update, owner=self, pool=g1.pool())
+    self._graph = (g1, g2)
 
   def graph_count(self):
     """hipGraphs a captured step replays (0: eager stepping)."""
@@ -683,10 +623,8 @@ class OnlineAdapter(object):
     return self._infer_left, self._infer_right
 
   def _replay(self, left, right):
-    if left.data_ptr() != self._static_left.data_ptr():
-      self._static_left.copy_(left)
-    if right.data_ptr() != self._static_right.data_ptr():
-      self._static_right.copy_(right)
+    copy_unless_same(self._static_left, left)
+    copy_unless_same(self._static_right, right)
     if not isinstance(self._graph, tuple):
       self._graph.replay()
     else:
@@ -742,15 +680,6 @@ def fill_step_scalars(buf, loss_sum, valid_count, fcs_sum, fcs_count):
     return buf
 
 
-def allreduce_step_scalars(buf, loss_sum, valid_count, fcs_sum, fcs_count, group=None):
-    """One 16-byte all-reduce(sum) of [valid-pixel count, loss sum, FCS sum, FCS count], issued BEFORE
-    backward: the reference's loss is the mean over the valid pixels of the whole batch (adapt.py:83),
-    so every rank must scale its local gradient by 1/N_total, not 1/N_rank."""
-    fill_step_scalars(buf, loss_sum, valid_count, fcs_sum, fcs_count)
-    dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=group)
-    return buf
-
-
 _COMM_STREAMS = {}
 
 
@@ -778,10 +707,3 @@ def allreduce_gradients_and_scalars(arena, group=None):
     step's four scalars riding behind it (313,702 floats at k=4; latency-bound on xGMI, hence one message)."""
     _all_reduce_on_comm_stream(arena.grads_and_scalars, group)
     return arena.grads_and_scalars
-
-
-def allreduce_gradients(flat_grads, group=None):
-    """ONE all-reduce(sum) of the flat gradient arena (313,698 floats at k=4): on xGMI this message is
-    latency-bound, so a single bucket beats per-tensor or per-layer buckets."""
-    _all_reduce_on_comm_stream(flat_grads, group)
-    return flat_grads

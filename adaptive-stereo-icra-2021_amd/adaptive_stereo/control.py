@@ -19,6 +19,7 @@ from enum import Enum
 import torch
 
 from . import _native as nat
+from .capture import refuse_nested, static_pair, warm_up_and_capture
 from .utils.stereo_reservoir import StereoReservoir
 
 MODES = ("NONSTOP", "VS", "ER", "VS+ER", "NONE")
@@ -269,12 +270,8 @@ class AdaptationLoop(object):
 
   def _bind_inputs(self, left, right, replay):
     if self._static is None:
-      pair = torch.cat([left, right])              # the two images halves of one buffer: the pair pass needs no copy
-      sl, sr = pair[:left.shape[0]], pair[left.shape[0]:]
-      srep = None
-      if replay is not None:
-        rpair = torch.cat([replay[0], replay[1]])
-        srep = (rpair[:replay[0].shape[0]], rpair[replay[0].shape[0]:], replay[2].clone())
+      sl, sr = static_pair(left, right)
+      srep = None if replay is None else static_pair(replay[0], replay[1]) + (replay[2].clone(),)
       self._static = (sl, sr, srep)
       self.state_machine.ovs.allocate(sl)
       return
@@ -300,31 +297,20 @@ class AdaptationLoop(object):
   def _capture(self, gate_enabled):
     """Warm-up on the capture stream with the gate shut (nothing is novel, nothing adapts: the reservoir, the parameters, both
     moments and the step count stay as they are), then the capture.  What a forward pass in train mode changes on its own — the
-    BatchNorm running statistics and counters, the FCS EMA — is put back afterwards, so the loop's state is the one it had."""
+    BatchNorm running statistics and counters, the FCS EMA — is put back afterwards, so the loop's state is the one it had.
+    (The loop captures only once the adapter's step plan is built, so the buffers saved are the buffers the graph updates.)"""
     a = self.adapter
-    a._refuse_nested_capture("AdaptationLoop capture")
-    bufs = [b for net in (a.stereo_net, a.feature_net) for b in net.buffers()]
-    saved = [b.clone() for b in bufs]
-    ema = a.fcs_smoothed.clone()
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-      for _ in range(2):
-        self._gated_body(float("-inf"), False, False)
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    a._capture_origin = side.cuda_stream
-    try:
-      with torch.cuda.graph(graph, stream=side, capture_error_mode="thread_local"):
-        self._graph_result = self._gated_body(self.ood_threshold, gate_enabled, True)
-    finally:
-      a._capture_origin = None
-    with torch.no_grad():
-      for b, v in zip(bufs, saved):
-        b.copy_(v)
-      a.fcs_smoothed.copy_(ema)
-    self._graph = graph
+    refuse_nested("AdaptationLoop capture")
+
+    def state():
+      named = {prefix + name: b for prefix, net in (("stereo.", a.stereo_net), ("feature.", a.feature_net))
+               for name, b in net.named_buffers()}
+      named["fcs_ema"] = a.fcs_smoothed
+      return named
+
+    self._graph, self._graph_result = warm_up_and_capture(
+      lambda: self._gated_body(float("-inf"), False, False), 2,
+      lambda: self._gated_body(self.ood_threshold, gate_enabled, True), owner=a, state=state)
 
   def _process_captured(self, left, right, batch_idx, replay):
     sm = self.state_machine

@@ -143,6 +143,29 @@ def rmw_order_reset(enabled):
     lib.as_wgrad_defer(1)
 
 
+class step_region(object):
+  """``with step_region(plan, bn_sync, multi_stream): forward / backward`` — the bracket around a step's launches: the StepPlan
+  (if any) begins, cross-replica BatchNorm is set, the multi-stream region opens; on the way out, exception or not, in the
+  reverse order.  The order matters: closing the region launches the deferred weight-gradient reductions and joins the region's
+  streams, which must happen before the plan ends.  ``resume`` / ``final``: StepPlan.begin's / StepPlan.end's."""
+  __slots__ = ("plan", "bn_sync", "multi_stream", "resume", "final", "prev")
+
+  def __init__(self, plan=None, bn_sync=None, multi_stream=True, resume=False, final=True):
+    self.plan, self.bn_sync, self.multi_stream, self.resume, self.final = plan, bn_sync, multi_stream, resume, final
+
+  def __enter__(self):
+    if self.plan is not None:
+      self.plan.begin(resume=self.resume)
+    self.prev = set_bn_sync(self.bn_sync)
+    rmw_order_reset(self.multi_stream)
+
+  def __exit__(self, *exc):
+    rmw_order_reset(False)
+    set_bn_sync(self.prev)
+    if self.plan is not None:
+      self.plan.end(final=self.final)
+
+
 class _DeferredReduce(object):
   """Inside a step's multi-stream region the ~30 slab reductions behind the weight-gradient kernels (4.5 us each, nothing
   reads their result before the optimizer) are recorded by the library and run in one launch when the region closes

@@ -16,10 +16,9 @@ FusedClipAdam, the whole step is captured into one hipGraph.  What is particular
     its first batch computes what a run of eager steps computes, bit for bit.
 The step issues no host sync.
 """
-import torch
-
 from . import hip_ops
 from .adaptation import FlatArena, FusedClipAdam
+from .capture import copy_unless_same, refuse_nested, static_pair, warm_up_and_capture
 from .utils.loss_functions import khamis_robust_loss_two_scale
 
 
@@ -49,17 +48,14 @@ class SupervisedTrainer(object):
     self.feature_net.train(); self.stereo_net.train()
     self.arena.rebind_grads()
     self.arena.zero_grads()
-    self.plan.begin()
-    hip_ops.rmw_order_reset(True)        # (the weight-gradient reductions of the step run as one launch when it closes)
-    try:
+    # (the weight-gradient reductions of the step run as one launch when the region closes; bn_sync=None changes nothing: this
+    # trainer has no cross-replica BatchNorm)
+    with hip_ops.step_region(self.plan, bn_sync=None):
       # each image with its own BatchNorm statistics, as two passes of the feature extractor have (train.py:20)
       fl, fr = self.feature_net.forward_pair(left, right)
       out = self.stereo_net(left, fl, fr, "l")
       losses = self._losses(gt, out)
       losses["total_loss"].backward()
-    finally:
-      hip_ops.rmw_order_reset(False)
-      self.plan.end()
     self.optimizer.step(clip=self.clip)
     result = {name: value.detach() for name, value in losses.items()}
     result["outputs"] = out
@@ -86,39 +82,22 @@ class SupervisedTrainer(object):
 
   def capture(self, left, right, gt, warmup=2):
     """Captures one step (forward, loss, backward, [clip,] Adam) for batches of this shape into a hipGraph; step() replays it
-    from then on.  Discipline of OnlineAdapter.capture: warm-up on a side stream, capture on that stream,
-    capture_error_mode="thread_local", no capture inside a capture; inputs are copied into static buffers before a replay
-    unless they already are those buffers (graph_inputs()).  The warm-up steps are undone: parameters, moments, step count and
-    BatchNorm buffers are what they were before the call."""
-    if torch.cuda.is_current_stream_capturing():
-      raise RuntimeError("SupervisedTrainer.capture: the current stream is already being captured; a capture inside a "
-                         "capture crashes hipStreamEndCapture on ROCm 7.2 — capture from an ordinary stream")
-    pair = torch.cat([left, right])      # one buffer, the two images its halves: the pair pass needs no concatenation copy
+    from then on (the capture rules: capture.py; forward_pair never forks, so there is no capture origin to record).  Inputs are
+    copied into static buffers before a replay unless they already are those buffers (graph_inputs()).  The warm-up steps are
+    undone: parameters, moments, step count and BatchNorm buffers are what they were before the call."""
+    refuse_nested("SupervisedTrainer.capture")
     self._graph = None
-    self._static = (pair[:left.shape[0]], pair[left.shape[0]:], gt.clone())
-    saved = {name: t.clone() for name, t in self._state_tensors().items()}
+    self._static = static_pair(left, right) + (gt.clone(),)
     count = self.optimizer.step_count
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-      for _ in range(max(2, warmup)):          # the first step a plan sees records it, the next one runs it
-        self._step_eager(*self._static)
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph, stream=side, capture_error_mode="thread_local"):   # the warm-up's stream: its pooled
-      self._static_result = self._step_eager(*self._static)                          # buffers are reused
-    with torch.no_grad():
-      for name, t in self._state_tensors().items():
-        t.copy_(saved[name])
+    step = lambda: self._step_eager(*self._static)
+    # (warm-up: the first step a plan sees records it, the next one runs it)
+    self._graph, self._static_result = warm_up_and_capture(step, max(2, warmup), step, state=self._state_tensors)
     self.optimizer.step_count = count          # capture only records, and the warm-up is undone
-    self._graph = graph
     return self
 
   def _replay(self, left, right, gt):
-    for src, dst in zip((left, right, gt), self._static):
-      if src.data_ptr() != dst.data_ptr():
-        dst.copy_(src)
+    for dst, src in zip(self._static, (left, right, gt)):
+      copy_unless_same(dst, src)
     self._graph.replay()
     self.optimizer.step_count += 1          # host mirror of the device-side counter
     return self._static_result

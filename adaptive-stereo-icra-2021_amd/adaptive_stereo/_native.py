@@ -217,6 +217,7 @@ _SIGNATURES = {
                                  c_vp, c_vp]),
   "as_adapt_gate": (c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.c_double, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
   "as_reservoir_store": (c_int, [c_vp, c_vp, c_i64, c_vp, c_int, c_vp, c_vp, c_vp]),
+  "as_pq_offer": (c_int, [c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
   "as_khamis2_workspace": (c_i64, [c_i64]),
   "as_khamis2_fwd": (c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
   "as_khamis2_bwd": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_float, c_vp, c_vp, c_vp]),
@@ -229,6 +230,8 @@ _SIGNATURES = {
   "as_disp_to_points": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, _P(DepthCamera), c_vp, c_vp, c_float, c_vp, c_i64, c_vp]),
   "as_voxel_cloud_finalize": (c_int, [c_vp, c_int, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
   "as_fcs_scores": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp]),
+  "as_image_entropy_workspace": (c_i64, [c_int]),
+  "as_image_entropy": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
   "as_lidar_zbuf_clear": (c_int, [c_vp, c_int, c_int, c_int, c_vp]),
   "as_lidar_project": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp]),
   "as_lidar_resolve_workspace": (c_i64, [c_int, c_int, c_int]),

@@ -124,6 +124,26 @@ def collect_scores(feature_net, stereo_net, batches, num_images, input_scale=0):
   return collector.scores()
 
 
+def collect_image_entropy(batches, num_images, input_scale=0):
+  """Scores [n,2] (n <= num_images) of the left image over `batches`, any iterable of dicts with ``color_l/{s}``: column 0 the
+  entropy of the 8-bit intensities, column 1 that of their horizontal differences (utils/entropy.py: EntropyCollector.add per
+  batch).  No network pass.  Stops once num_images rows are in; one read-back, at the end."""
+  from .utils.entropy import EntropyCollector
+  key = "color_l/{}".format(int(input_scale))
+  collector, seen = None, 0
+  for inputs in batches:
+    if seen >= num_images:
+      break
+    left = nat.f32c(inputs[key].cuda())
+    if collector is None:
+      collector = EntropyCollector(num_images, device=left.device)
+    collector.add(left)
+    seen += left.shape[0]
+  if collector is None:
+    return torch.zeros(0, 2, dtype=torch.float32)
+  return collector.scores()
+
+
 def _as_f32_1d(scores, name):
   t = torch.as_tensor(scores).detach()
   if t.dim() != 1 or t.numel() == 0:

@@ -93,3 +93,61 @@ extern "C" int as_reservoir_store(const float* left, const float* right, int64_t
   AS_CHECK_LAUNCH("as_reservoir_store");
   return AS_OK;
 }
+
+// The reference's utils/stereo_priority_queue.py as one wave: keeps the `capacity` smallest keys (key = value for a min heap,
+// -value for a max heap).  Every lane reads the same scalars and takes the same branches; the duplicate search and the search for
+// the worst member are lane-strided; lane 0 writes.  state = [size, offers, adds] (int64).
+__global__ __launch_bounds__(64) void pq_offer_kernel(const float* __restrict__ value, const int32_t* __restrict__ index,
+                                                       int capacity, int min_heap, int64_t* __restrict__ state,
+                                                       int32_t* __restrict__ indices, float* __restrict__ keys,
+                                                       int32_t* __restrict__ out_slot) {
+  const int lane = threadIdx.x;
+  int64_t size = state[0];
+  const float v = value[0];
+  const float key = min_heap ? v : -v;
+  const int32_t idx = index[0];
+  int slot = -1;
+  if (key == key) {                                // a NaN is refused: it has no place in the order (wave-uniform)
+    int dup = 0;
+    for (int64_t i = lane; i < size; i += 64) dup |= (indices[i] == idx);
+    if (!__any(dup)) {
+      if (size < capacity) {
+        slot = (int)size;
+        size += 1;
+      } else {
+        // the worst member: the maximum by (key, index)
+        float wk = 0.f;
+        int32_t wi = 0;
+        int ws = -1;
+        for (int64_t i = lane; i < size; i += 64) {
+          const float k = keys[i];
+          const int32_t j = indices[i];
+          if (ws < 0 || k > wk || (k == wk && j > wi)) { wk = k; wi = j; ws = (int)i; }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+          const float k = __shfl_xor(wk, o, 64);
+          const int32_t j = __shfl_xor(wi, o, 64);
+          const int s = __shfl_xor(ws, o, 64);
+          if (s >= 0 && (ws < 0 || k > wk || (k == wk && j > wi))) { wk = k; wi = j; ws = s; }
+        }
+        if (key < wk) slot = ws;                   // strictly better only: an offer equal to the worst key is refused
+      }
+    }
+  }
+  if (lane == 0) {
+    if (slot >= 0) { indices[slot] = idx; keys[slot] = key; }
+    state[0] = size; state[1] += 1; state[2] += (slot >= 0);
+    out_slot[0] = slot;
+  }
+}
+
+extern "C" int as_pq_offer(const float* value, const int32_t* index, int capacity, int min_heap, int64_t* state,
+                           int32_t* indices, float* keys, int32_t* out_slot, void* stream) {
+  AS_CHECK_ARG(value && index && state && indices && keys && out_slot && capacity >= 1, "as_pq_offer: bad argument");
+  AS_CHECK_ARG(((uintptr_t)state & 7) == 0, "as_pq_offer: state must be 8-byte aligned");
+  hipLaunchKernelGGL(pq_offer_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, value, index, capacity, min_heap, state, indices,
+                     keys, out_slot);
+  AS_CHECK_LAUNCH("as_pq_offer");
+  return AS_OK;
+}

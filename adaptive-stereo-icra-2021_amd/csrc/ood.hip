@@ -105,6 +105,11 @@ __global__ void fcs_advance_kernel(int32_t* cursor, int32_t* dropped, int B, int
   if (cursor && c >= 0) *cursor = c > FCS_CURSOR_MAX - B ? FCS_CURSOR_MAX : c + B;
 }
 
+// the same cursor rule for every collector kernel of the library (entropy.hip appends its rows by it)
+void as_cursor_advance_enqueue(hipStream_t st, int32_t* cursor, int32_t* dropped, int B, int capacity) {
+  hipLaunchKernelGGL(fcs_advance_kernel, dim3(1), dim3(1), 0, st, cursor, dropped, B, capacity);
+}
+
 extern "C" int as_fcs_scores(const float* logits, int B, int D, int H, int W, float* fcs_mean, float* fcs_median, float* scores,
                              int capacity, int32_t* cursor, int32_t* dropped, void* stream) {
   AS_CHECK_ARG(logits && B > 0 && B <= FCS_MAX_BATCH && H > 0 && W > 0 && (int64_t)H * W <= ((int64_t)1 << 30),
@@ -128,7 +133,7 @@ extern "C" int as_fcs_scores(const float* logits, int B, int D, int H, int W, fl
     hipLaunchKernelGGL(fcs_scores_kernel<64>, grid, block, 0, st, logits, D, HW, fcs_mean, fcs_median, scores, cur, capacity);
   AS_CHECK_LAUNCH("as_fcs_scores");
   if (cursor || dropped) {
-    hipLaunchKernelGGL(fcs_advance_kernel, dim3(1), dim3(1), 0, st, cursor, dropped, B, capacity);
+    as_cursor_advance_enqueue(st, cursor, dropped, B, capacity);
     AS_CHECK_LAUNCH("as_fcs_scores(cursor)");
   }
   return AS_OK;

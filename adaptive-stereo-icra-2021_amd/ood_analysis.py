@@ -3,16 +3,25 @@
 score per image (adaptive_stereo.ood: one launch per batch, one read-back per domain), and writes
 
   <output_folder>/train_fcs.pt, novel_fcs.pt   the max-minus-mean scores, as the reference saves them
-  <output_folder>/ood.json                     mu, sigma, threshold, n, the precision/recall sweep and the two histograms
+                                               (train_<score>.pt, novel_<score>.pt for another --score)
+  <output_folder>/ood.json                     score (the --score analysed), mu, sigma, threshold, n, the precision/recall
+                                               sweep and the two histograms
 
   python ood_analysis.py --load_weights_folder W --stereonet_k 4 \\
       --train_dataset_path P --train_dataset_name VirtualKitti --train_split virtual_kitti_clone \\
       --novel_dataset_path Q --novel_dataset_name KittiRaw --novel_split kitti_raw_city_adapt --percentile 0.05
+
+--score picks the per-image score: fcs_mean (the default, max-minus-mean), fcs_median (max-minus-median), or the entropy of the
+left image's intensities (entropy_gray) or of their horizontal differences (entropy_grad), which need no network pass and no
+weights (adaptive_stereo.utils.entropy).
 """
 import argparse
 import json
 import os
 import random
+
+
+SCORES = {"fcs_mean": ("fcs", 0), "fcs_median": ("fcs", 1), "entropy_gray": ("entropy", 0), "entropy_grad": ("entropy", 1)}
 
 
 def parse(args=None):
@@ -33,6 +42,7 @@ def parse(args=None):
   p.add_argument("--num_novel", type=int, default=1000)
   p.add_argument("--num_workers", type=int, default=4)
   p.add_argument("--output_folder", type=str, default="ood")
+  p.add_argument("--score", type=str, default="fcs_mean", choices=sorted(SCORES), help="the per-image score to analyse")
   opt = p.parse_args(args)
   if not (0.01 <= opt.percentile <= 0.99):
     p.error("--percentile must lie in [0.01, 0.99]")
@@ -51,10 +61,13 @@ def main(args=None):
   torch.manual_seed(123)
   random.seed(123)
   s = opt.stereonet_input_scale
-  feature_net = FeatureExtractorNetwork(opt.stereonet_k).cuda()
-  stereo_net = StereoNet(opt.stereonet_k, 1, s).cuda()
-  feature_net.load_state_dict(torch.load(os.path.join(opt.load_weights_folder, "feature_net.pth")), strict=True)
-  stereo_net.load_state_dict(torch.load(os.path.join(opt.load_weights_folder, "stereo_net.pth")), strict=True)
+  family, column = SCORES[opt.score]
+  tag = "fcs" if opt.score == "fcs_mean" else opt.score
+  if family == "fcs":
+    feature_net = FeatureExtractorNetwork(opt.stereonet_k).cuda()
+    stereo_net = StereoNet(opt.stereonet_k, 1, s).cuda()
+    feature_net.load_state_dict(torch.load(os.path.join(opt.load_weights_folder, "feature_net.pth")), strict=True)
+    stereo_net.load_state_dict(torch.load(os.path.join(opt.load_weights_folder, "stereo_net.pth")), strict=True)
 
   scores = {}
   for domain, num in (("train", opt.num_train), ("novel", opt.num_novel)):
@@ -62,18 +75,22 @@ def main(args=None):
                             getattr(opt, domain + "_split"), opt.height, opt.width, getattr(opt, domain + "_subsplit"),
                             scales=[s], load_disp_left=False, load_disp_right=False)
     loader = DataLoader(dataset, opt.batch_size, shuffle=True, pin_memory=True, drop_last=False, num_workers=opt.num_workers)
-    scores[domain] = ood.collect_scores(feature_net, stereo_net, loader, num, input_scale=s)[:, 0].cpu()
-    print("{}: {} images, FCS {:.4f} .. {:.4f}".format(domain, len(scores[domain]), float(scores[domain].min()),
-                                                       float(scores[domain].max())))
+    if family == "fcs":
+      both = ood.collect_scores(feature_net, stereo_net, loader, num, input_scale=s)
+    else:
+      both = ood.collect_image_entropy(loader, num, input_scale=s)
+    scores[domain] = both[:, column].cpu()
+    print("{}: {} images, {} {:.4f} .. {:.4f}".format(domain, len(scores[domain]), "FCS" if tag == "fcs" else opt.score,
+                                                      float(scores[domain].min()), float(scores[domain].max())))
 
   os.makedirs(opt.output_folder, exist_ok=True)
-  torch.save(scores["train"], os.path.join(opt.output_folder, "train_fcs.pt"))
-  torch.save(scores["novel"], os.path.join(opt.output_folder, "novel_fcs.pt"))
+  torch.save(scores["train"], os.path.join(opt.output_folder, "train_%s.pt" % tag))
+  torch.save(scores["novel"], os.path.join(opt.output_folder, "novel_%s.pt" % tag))
   threshold, mu, sigma = ood.ood_threshold(scores["train"], opt.percentile)
   pr = ood.precision_recall(scores["train"], scores["novel"])
   recall_fixed, precision_fixed = ood.strictly_decreasing_precision(pr["precision"], pr["recall"])
   edges, density_train, density_novel = ood.fcs_histogram(scores["train"], scores["novel"])
-  result = dict(mu=mu, sigma=sigma, threshold=threshold, percentile=opt.percentile,
+  result = dict(score=opt.score, mu=mu, sigma=sigma, threshold=threshold, percentile=opt.percentile,
                 n=dict(train=len(scores["train"]), novel=len(scores["novel"])),
                 precision_recall={k: v.tolist() for k, v in pr.items()},
                 precision_recall_monotone=dict(recall=recall_fixed.tolist(), precision=precision_fixed.tolist()),

@@ -685,6 +685,20 @@ int as_adapt_gate(const float* fcs_smoothed, const float* loss, const int32_t* b
 int as_reservoir_store(const float* left, const float* right, int64_t n, const int32_t* slot_dev, int capacity,
                        float* buf_left, float* buf_right, void* stream);
 
+/* ---- the K best pairs of a stream on the device — utils/stereo_priority_queue.py ---------------------
+ * as_pq_offer: one offer to a queue that keeps the `capacity` smallest keys, by one wave.  Device inputs: value (fp32), index
+ * (int32).  key = value for min_heap != 0, else -value (fp32, exact).  state = [size, offers, adds] (int64, 8-byte aligned),
+ * indices[capacity] (int32) and keys[capacity] (fp32) persist; rows [0, size) are the members, in no particular order.
+ *   offers += 1
+ *   refused (out_slot = -1, nothing else written) when index is in indices[0:size]
+ *   size < capacity: out_slot = size, size += 1
+ *   else: the worst member is the maximum by (key, index); out_slot = its row when key < its key (strictly), else -1
+ *   a slot: indices[slot] = index, keys[slot] = key, adds += 1
+ * One deviation from the reference, ours: a NaN value is always refused (the reference's heap would keep it below capacity and
+ * lose its order).  as_reservoir_store with out_slot as its slot_dev then copies the pair into the row. */
+int as_pq_offer(const float* value, const int32_t* index, int capacity, int min_heap, int64_t* state, int32_t* indices,
+                float* keys, int32_t* out_slot, void* stream);
+
 /* ---- supervised two-scale loss — train.py:215, utils/loss_functions.py:18-38 with scales = [s, s + k] ----------
  * pred0 = pred_disp_l/s, up = pred_disp_l/(s+k) (the up-sampled coarse map), gt: n elements each.  One pass over gt:
  * out4 = [khamis(pred0, gt), khamis(up, gt), out4[0] + out4[1] (fp32), max(count(gt > 0), 1)]; NaN in gt is not valid.
@@ -782,6 +796,31 @@ int as_voxel_cloud_finalize(void* table, int B, int64_t slots, int cap, void* re
  *                         that contains the call appends on every replay. */
 int as_fcs_scores(const float* logits, int B, int D, int H, int W, float* fcs_mean, float* fcs_median, float* scores,
                   int capacity, int32_t* cursor, int32_t* dropped, void* stream);
+
+/* ---- per-image entropy of intensities and horizontal differences (csrc/entropy.hip) — utils/entropy.py:11-21,31-44 ------
+ * One pass over img [B][C][H][W] (dense fp32).  Per image b, over its whole [C][H][W] block (the reference flattens whatever it
+ * is given), all in integers:
+ *   v            (int32)(255.0f * x): the product rounded to fp32, then truncated toward zero (x = -0.001 gives v = 0).
+ *                The reference's .int() is undefined for what follows, so this rule is OURS: a pixel whose product is NaN,
+ *                +-inf or of magnitude >= 2^31 is INVALID; it enters no bin and no difference it takes part in enters one.
+ *   count_g[v]   += 1 for 0 <= v <= 255; other values are ignored (torch.histc(min=0, max=255) ignores them).
+ *   count_d[q]   += 1 for d = v[y][x+1] - v[y][x] inside a row of a plane (never across a row end, a plane or an image; v not
+ *                range-limited) with -255 <= d <= 255 and q = min((d + 255) * 256 / 510, 255) in integer division; other
+ *                differences are ignored.
+ *   scores       row r = (cursor ? *cursor : 0) + b holds, when 0 <= r < capacity, two floats at scores + 2 * r:
+ *                (float)(-S) with S = the fp64 sum over bins 0..255 in that order, from 0.0, of p * log2(p) for every count > 0,
+ *                p = (double)count / (double)N; column 0: count_g and N = H * W, column 1: count_d and N = H * (W - 1).  N is the
+ *                PLANE's size for every C, as the reference divides by shape[-2] * shape[-1].  W == 1: column 1 is NaN
+ *                (0x7FC00000), the reference's 0 / 0.  Integer counts and a fixed order: the same bits on every run.
+ *   hist         NULL or [B][2][256] uint32: count_g then count_d of image b (indexed by b, not by the cursor).
+ *   cursor, dropped   exactly as_fcs_scores' (a second, one-lane launch); each may be NULL.
+ * workspace: as_image_entropy_workspace(B) bytes (0 for a B outside [1, 65535]), 4-byte aligned, ALL ZERO before its first
+ * use; every call leaves it all zero again (the last workgroup of an image zeroes that image's slice), so a captured graph
+ * needs no memset node.  A workspace serves one call at a time.  B <= 65535, C * H * W <= 2^30, capacity >= 1; a bad argument
+ * returns AS_ERR_ARG before any launch.  Allocates nothing, never waits, capturable. */
+int64_t as_image_entropy_workspace(int B);
+int as_image_entropy(const float* img, int B, int C, int H, int W, float* scores, int capacity, int32_t* cursor,
+                     int32_t* dropped, uint32_t* hist, void* workspace, void* stream);
 
 /* ---- LiDAR ground truth: Velodyne scan -> sparse depth and disparity (csrc/lidar.hip) — scripts/export_gt_disp.py:86-115,156-162 ----
  * What the reference's export script computes on the host per frame: the scan is projected into a rectified camera, the nearest

@@ -152,6 +152,7 @@ _SIGNATURES = {
                            c_vp, c_vp, c_int, c_vp, c_vp]),
   "as_trunk_finish_bwd": (c_int, [c_vp, c_int, c_int, _P(c_vp), _P(c_vp), c_int, c_vp]),
   "as_agg_tail_ok": (c_int, [_P(Pcl)]),
+  "as_agg_tail_fwd_positions": (c_int, [_P(Pcl)]),
   "as_agg_tail_fwd": (c_int, [c_vp, _P(Pcl), c_vp, c_vp, _P(BnMerge), c_vp, c_vp, c_vp, c_float, c_vp, c_vp, c_vp, c_vp, c_vp]),
   "as_conv3d_out_fwd": (c_int, [c_vp, _P(Pcl), c_vp, c_vp, c_vp, c_vp]),
   "as_conv3d_out_bwd_workspace": (c_i64, [_P(Pcl)]),
@@ -177,6 +178,7 @@ _SIGNATURES = {
   "as_softargmax_bwd": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp]),
   "as_agg_tail_bwd_ok": (c_int, [_P(Pcl)]),
   "as_agg_tail_bwd_workspace": (c_i64, [_P(Pcl)]),
+  "as_agg_tail_bwd_columns": (c_int, [_P(Pcl)]),
   "as_agg_tail_bwd": (c_int, [c_vp, c_vp, c_vp, c_vp, _P(Pcl), c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp]),
   "as_upsample_bilinear_fwd": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_int, c_int, c_float, c_vp]),
   "as_upsample_bilinear_bwd": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_int, c_int, c_float, c_vp]),

@@ -401,13 +401,17 @@ static int tail_launch_t(const TailArgs& a, int grid, int lds_bytes, hipStream_t
   hipLaunchKernelGGL((agg_tail_kernel<IN, NK, OUT>), dim3(grid), dim3(256), lds_bytes, st, a);
   return AS_OK;
 }
+// positions per workgroup of the direct kernel: 16 while 32 would give fewer than two workgroups per CU (4 pairs at 24 x 78:
+// 240 of 32).  npos = positions of the flattened padded plane, (H - 1) Wp + W.  The launcher and as_agg_tail_fwd_positions.
+static int tail_direct_positions(int B, int npos) {
+  return ((long)B * as_div_up(npos, 32) < 512 && npos >= 16) ? 16 : 32;
+}
 template <int IN, bool OUT>
 static int tail_launch_direct(const TailArgs& a0, hipStream_t st) {
-  // 16 positions per workgroup while 32 would give fewer than two workgroups per CU (4 pairs at 24 x 78: 240 of 32)
   TailArgs a = a0;
   const int B = a.g.B;
-  const bool small = (long)B * as_div_up(a.npos, 32) < 512 && a.npos >= 16;
-  const int npos = small ? 16 : 32;
+  const int npos = tail_direct_positions(B, a.npos);
+  const bool small = npos == 16;
   a.tiles_per_plane = as_div_up(a.npos, npos);
   const int grid = B * a.tiles_per_plane;
   const int lds = BN_MERGE_SCRATCH_BYTES + TAIL_MAXD * npos * 4 + TAIL_TABLE_BYTES;
@@ -424,6 +428,16 @@ static int tail_launch_nk(const TailArgs& a, int grid, int lds_bytes, hipStream_
   if (nk <= 6) return tail_launch_t<IN, 6, OUT>(a, grid, lds_bytes, st);
   if (nk <= 8) return tail_launch_t<IN, 8, OUT>(a, grid, lds_bytes, st);
   return tail_launch_t<IN, 12, OUT>(a, grid, lds_bytes, st);
+}
+
+// read-only route query: positions per workgroup as_agg_tail_fwd would launch with for this geometry (16 or 32; 0: refused)
+extern "C" int as_agg_tail_fwd_positions(const as_pcl* g) {
+  if (as_agg_tail_ok(g) != 1) return 0;
+#ifdef TAIL_FIRST_GENERATION
+  return 32;
+#else
+  return tail_direct_positions(g->B, (g->H - 1) * (g->W + 2 * g->pw) + g->W);
+#endif
 }
 
 extern "C" int as_agg_tail_fwd(const float* x, const as_pcl* g, const float* in_scale, const float* in_shift,

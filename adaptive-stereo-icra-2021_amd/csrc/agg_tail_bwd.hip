@@ -238,6 +238,16 @@ extern "C" int64_t as_agg_tail_bwd_workspace(const as_pcl* g) {
   return (int64_t)kMaxGroups * (27 * 32 + 1);
 }
 
+// columns per unit: the launcher's decision and as_agg_tail_bwd_columns
+static int tail_bwd_columns(const as_pcl* g) {
+  return (long)g->B * g->H * ((g->W + 25) / 26) > kMaxGroups ? 26 : 13;
+}
+
+// read-only route query: columns per unit as_agg_tail_bwd would launch with for this geometry (13 or 26; 0: refused)
+extern "C" int as_agg_tail_bwd_columns(const as_pcl* g) {
+  return as_agg_tail_bwd_ok(g) == 1 ? tail_bwd_columns(g) : 0;
+}
+
 // logits [B][D][H][W] (saved by the forward pass); g_pred [B][H][W] and g_logits_in [B][D][H][W] may each be NULL (zero);
 // a, g_a: PCL of geometry g (halo >= 1); w [32][27]; g_w [32][27] and g_bias [1] are overwritten, or added to with accumulate.
 extern "C" int as_agg_tail_bwd(const float* logits, const float* g_pred, const float* g_logits_in, const float* a,
@@ -249,8 +259,8 @@ extern "C" int as_agg_tail_bwd(const float* logits, const float* g_pred, const f
   TailBwdArgs p;
   p.logits = logits; p.g_pred = g_pred; p.g_in = g_logits_in; p.a = a; p.w = w; p.g_a = g_a; p.partial = workspace;
   p.g = as_make_dev(g);
-  const bool wide = (long)g->B * g->H * ((g->W + 25) / 26) > kMaxGroups;
-  const int XC = wide ? 26 : 13;
+  const int XC = tail_bwd_columns(g);
+  const bool wide = XC == 26;
   p.nxc = (g->W + XC - 1) / XC;
   p.units = g->B * g->H * p.nxc;
   const int groups = p.units < kMaxGroups ? p.units : kMaxGroups;

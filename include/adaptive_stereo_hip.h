@@ -290,6 +290,10 @@ int as_agg3d_fwd(const float* x, const as_pcl* g, const float* packed_w, const f
  *   logits           dense [B,D,H,W];  pred, fcs: dense float [B,H,W];  argmax: int32 [B,H,W] (first maximum, as torch.argmax);
  *                    argmax and fcs may be NULL */
 int as_agg_tail_ok(const as_pcl* g);
+/* read-only route query: positions of the flattened padded plane per workgroup that as_agg_tail_fwd launches with for this
+ * geometry, 16 (agg_tail_direct_kernel<.., 16>: B * ceil(npos / 32) < 512, npos = (H - 1)(W + 2) + W) or 32; 0 where
+ * as_agg_tail_ok(g) == 0.  The two give equal logits by design: only the query tells which kernel ran. */
+int as_agg_tail_fwd_positions(const as_pcl* g);
 int as_agg_tail_fwd(const float* x, const as_pcl* g, const float* in_scale, const float* in_shift,
                     const as_bn_merge* in_bn, float* a_out,
                     const float* w, const float* bias, float slope, float* logits, float* pred,
@@ -478,6 +482,9 @@ int as_softargmax_bwd(const float* logits, const float* g_pred, const float* g_l
  * workspace: as_agg_tail_bwd_workspace(g) floats.  as_agg_tail_bwd_ok(g) == 0: use as_softargmax_bwd + as_conv3d_out_bwd. */
 int as_agg_tail_bwd_ok(const as_pcl* g);
 int64_t as_agg_tail_bwd_workspace(const as_pcl* g);
+/* read-only route query: columns per unit that as_agg_tail_bwd launches with for this geometry, 13 (agg_tail_bwd_kernel<13>:
+ * B * H * ceil(W / 26) <= 768) or 26; 0 where as_agg_tail_bwd_ok(g) == 0 */
+int as_agg_tail_bwd_columns(const as_pcl* g);
 int as_agg_tail_bwd(const float* logits, const float* g_pred, const float* g_logits_in, const float* a, const as_pcl* g,
                     const float* w, float* g_a, float* g_w, float* g_bias, int accumulate, float* workspace, void* stream);
 

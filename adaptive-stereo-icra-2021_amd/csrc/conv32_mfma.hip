@@ -1045,6 +1045,8 @@ extern "C" int as_conv32_wino_bwd(const float* x, const as_pcl* gin, const float
                                   float* workspace, void* stream) {
   if (int e = check_conv(gin, gout, s, "as_conv32_wino_bwd")) return e;
   AS_CHECK_ARG(x && dW && workspace, "as_conv32_wino_bwd: null pointer");
+  // (both launches below take gout alone: x laid out in another padded geometry would be read with the wrong strides)
+  AS_CHECK_ARG(conv32_wino_applicable(gin, gout, s), "as_conv32_wino_bwd: configuration not supported (as_conv32_wino_ok() == 0)");
   AS_CHECK_ARG(g_x != x && g_z != x, "as_conv32_wino_bwd: outputs must not alias inputs or each other");
   if (int e = as_conv32_wino_bwd_data(g_a, z, gout, s, wino_wt, scale, shift, mean, coef, slope, next_z, next_scale, next_shift,
                                       next_mean, g_z, g_x, next_bn_workspace, stream)) return e;

@@ -234,6 +234,7 @@ _SIGNATURES = {
   "as_fcs_scores": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp]),
   "as_image_entropy_workspace": (c_i64, [c_int]),
   "as_image_entropy": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
+  "as_cost_volume_probe": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp]),
   "as_lidar_zbuf_clear": (c_int, [c_vp, c_int, c_int, c_int, c_vp]),
   "as_lidar_project": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp]),
   "as_lidar_resolve_workspace": (c_i64, [c_int, c_int, c_int]),

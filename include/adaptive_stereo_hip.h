@@ -829,6 +829,34 @@ int64_t as_image_entropy_workspace(int B);
 int as_image_entropy(const float* img, int B, int C, int H, int W, float* scores, int capacity, int32_t* cursor,
                      int32_t* dropped, uint32_t* hist, void* workspace, void* stream);
 
+/* ---- cost-volume probe: extreme-contrast pixels and rank profile (csrc/cv_probe.hip) — evaluation/cost_volume_analysis.py:82-92 ----
+ * One pass over logits [B][D][H][W] (dense fp32, the tensor as_fcs_scores reads), 1 <= D <= 64, B <= 65535, H * W <= 2^30,
+ * capacity >= 1; gt NULL or [B][1][H][W] fp32 (the coarse ground truth).  A bad argument returns AS_ERR_ARG before any launch.
+ * Allocates nothing, never waits, capturable.  Compiled with `#pragma clang fp contract(off)`: every expression below is a
+ * sequence of single IEEE fp32 operations in the written order.
+ *   map f        per pixel p = row * W + col, as_fcs_scores' fcs_mean: `sum += v; if (v > m1) { m2 = m1; m1 = v; } else if
+ *                (v > m2) m2 = v;` over d in increasing order from sum = 0.f, m1 = m2 = -inf; mean_rest = (sum - m1 - m2) /
+ *                (float)(D - 2) and f = m1 - mean_rest for D > 2; f = 0 for D <= 2; f = NaN when any of the D values is NaN.  For
+ *                finite logits the same bits as as_fcs_scores and as_softargmax_fwd give.
+ *   selection    torch's argmax (which = 0, "hi") and argmin (which = 1, "lo") of the flattened map: the smallest p whose f is NaN
+ *                if any pixel's is (both times), otherwise the smallest p with f[p] == the extreme.  Values compare as fp32 numbers
+ *                (-0.f equals +0.f).  The reduction carries (value, p) and breaks value ties on p, never on a lane number.
+ * Row r = (cursor ? *cursor : 0) + b is written when 0 <= r < capacity.  Outputs, each may be NULL (at least one is not; a NULL
+ * output is not written):
+ *   pix     [capacity][2][3] int32   row, col, d_max (the smallest d holding m1; -1 at a NaN pixel)
+ *   vals    [capacity][2][5] fp32    f, m1, m2, mean_rest, gt[b][row][col].  The gt entry is NaN without gt; D <= 2: mean_rest is
+ *                                    NaN (and m2 is -inf for D == 1); at a NaN pixel m1, m2 and mean_rest are NaN; every such NaN
+ *                                    is 0x7FC00000.  In every other case f == m1 - mean_rest bit for bit.
+ *   slices  [capacity][2][D] fp32    the D logits of the pixel, copied bit for bit
+ *   profile [capacity][D] fp32       profile[r][j] = (float)(S_j / (double)(H * W)), S_j the fp64 sum over the image's pixels of the
+ *                                    j-th largest of the pixel's D values (j = 0 is the maximum).  A pixel holding a NaN makes every
+ *                                    S_j of its image NaN.  No floating-point atomics; the order of the sum is a function of the
+ *                                    shape only, so the same input gives the same bits on every run (the order itself is not part
+ *                                    of the contract).
+ *   cursor, dropped                  exactly as_fcs_scores' (a second, one-lane launch); each may be NULL. */
+int as_cost_volume_probe(const float* logits, const float* gt, int B, int D, int H, int W, int32_t* pix, float* vals,
+                         float* slices, float* profile, int capacity, int32_t* cursor, int32_t* dropped, void* stream);
+
 /* ---- LiDAR ground truth: Velodyne scan -> sparse depth and disparity (csrc/lidar.hip) — scripts/export_gt_disp.py:86-115,156-162 ----
  * What the reference's export script computes on the host per frame: the scan is projected into a rectified camera, the nearest
  * return is kept per pixel, depth becomes disparity = baseline * fx / depth and is stored as uint16 = 128 * disp.

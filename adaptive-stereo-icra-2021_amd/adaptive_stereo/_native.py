@@ -231,6 +231,10 @@ _SIGNATURES = {
   "as_voxel_table_clear": (c_int, [c_vp, c_int, c_i64, c_vp]),
   "as_disp_to_points": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, _P(DepthCamera), c_vp, c_vp, c_float, c_vp, c_i64, c_vp]),
   "as_voxel_cloud_finalize": (c_int, [c_vp, c_int, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+  "as_disp_to_points_gated": (c_int, [c_vp, c_vp, c_vp, c_float, c_int, c_int, c_int, c_int, _P(DepthCamera), c_vp, c_vp, c_float, c_vp,
+                                      c_i64, c_vp, c_vp]),
+  "as_disp_confidence": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
+  "as_sparsification": (c_int, [c_vp, c_vp, c_vp, c_i64, c_float, c_float, c_int, c_float, c_vp, c_vp, c_vp, c_vp, c_vp]),
   "as_fcs_scores": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp]),
   "as_image_entropy_workspace": (c_i64, [c_int]),
   "as_image_entropy": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),

@@ -11,6 +11,11 @@ deliberately differs from the node.
   cloud = proj.voxel_cloud(outputs["pred_disp_l/0"], left) # no allocation, no synchronisation: graph-capturable
   data = cloud.to_pointcloud2_bytes(0)                     # synchronises
 
+With a confidence map (adaptive_stereo.confidence) the cloud keeps only the pixels the network is sure of:
+
+  conf = disparity_confidence(outputs["cost_volume_l/4"], kinds=("mass",))["mass"]
+  cloud = proj.voxel_cloud(outputs["pred_disp_l/0"], left, confidence=conf, conf_min=0.8)   # cloud.rejected [B]
+
 The views a method returns alias the projector's buffers: the next call overwrites them.
 """
 import ctypes
@@ -44,13 +49,15 @@ class StereoCamera(object):
 
 class VoxelCloud(object):
   """Device views of one voxel_cloud() call.  records [B,cap,4] int32 (x, y, z as fp32 bits, then R << 16 | G << 8 | B), voxel
-  [B,cap,3] int32, count [B,cap] int32, n [B] int32 (rows in use per image), dropped [B] int32.  Rows at or beyond n[b] hold
-  leftovers of earlier calls; the order of rows within an image is unspecified."""
+  [B,cap,3] int32, count [B,cap] int32, n [B] int32 (rows in use per image), dropped [B] int32, rejected [B] int32 (pixels valid
+  by depth that failed the confidence gate; None for a call without one).  Rows at or beyond n[b] hold leftovers of earlier
+  calls; the order of rows within an image is unspecified."""
 
-  def __init__(self, batch, records, voxel, count, n, dropped):
+  def __init__(self, batch, records, voxel, count, n, dropped, rejected=None):
     self.batch = batch
     self.records, self.voxel, self.count = records[:batch], voxel[:batch], count[:batch]
     self.n, self.dropped = n[:batch], dropped[:batch]
+    self.rejected = None if rejected is None else rejected[:batch]
 
   @property
   def xyz(self):
@@ -75,7 +82,11 @@ class VoxelCloud(object):
 
 class DepthProjector(object):
   """Disparity [B,1,H,W] -> depth / organised cloud / voxel cloud at pyramid level ``pyramid_scale`` (0, 1 or 2).  The defaults
-  are the node's Config.  depth(), organized() and voxel_cloud() allocate nothing and never synchronise."""
+  are the node's Config.  depth(), organized() and voxel_cloud() allocate nothing and never synchronise.
+
+  organized() and voxel_cloud() take a confidence map [B,hc,wc] or [B,1,hc,wc] of any coarse size together with conf_min: the
+  map is up-sampled to (h, w) into ``confidence_level`` (as_upsample_bilinear_fwd, gain 1) and a pixel that is valid by depth is
+  kept only when its confidence there is >= conf_min (a NaN confidence rejects it)."""
 
   def __init__(self, height, width, camera, batch=1, pyramid_scale=2, max_depth=100.0, depth_scale=100.0, depth_trunc=80.0,
                voxel_size=0.15, device="cuda", table_slots=None):
@@ -114,6 +125,9 @@ class DepthProjector(object):
     self._count = torch.zeros(B, self.cap, dtype=torch.int32, device=dev)
     self._n = torch.zeros(B, dtype=torch.int32, device=dev)
     self._dropped = torch.zeros(B, dtype=torch.int32, device=dev)
+    self._conf = torch.zeros(B, 1, h, w, dtype=torch.float32, device=dev)
+    self._rejected = torch.zeros(B, dtype=torch.int32, device=dev)
+    self._conf_batch = 0
     with torch.cuda.device(dev):
       # once: as_voxel_cloud_finalize hands back empty every slot it read, so no later call clears the table
       nat.call("as_voxel_table_clear", nat.ptr(self._table), B, self.slots, nat.stream())
@@ -133,12 +147,47 @@ class DepthProjector(object):
                            % (self._depth.device, t.dtype, t.device, t.is_contiguous()))
     return b
 
-  def _run(self, disp, left_img, depth, xyz, table):
+  @property
+  def confidence_level(self):
+    """[B,1,h,w]: the confidence the last gated call compared with conf_min, at the pyramid level's resolution."""
+    return self._conf[:self._conf_batch]
+
+  def _check_confidence(self, b, confidence, conf_min):
+    """The coarse size (hc, wc) of a usable confidence map; None for a call without a gate."""
+    if confidence is None and conf_min is None:
+      return None
+    if confidence is None or conf_min is None:
+      raise ValueError("DepthProjector: confidence and conf_min go together (got confidence %s, conf_min %r)"
+                       % ("None" if confidence is None else tuple(confidence.shape), conf_min))
+    nat.require_gpu(confidence)
+    shape = tuple(confidence.shape)
+    if confidence.dim() == 4 and shape[1] == 1:
+      shape = (shape[0],) + shape[2:]
+    if len(shape) != 3 or shape[0] != b or shape[1] < 1 or shape[2] < 1:
+      raise RuntimeError("DepthProjector: confidence has shape %s, expected [%d,hc,wc] or [%d,1,hc,wc]"
+                         % (tuple(confidence.shape), b, b))
+    if confidence.dtype != torch.float32 or not confidence.is_contiguous() or confidence.device != self._depth.device:
+      raise RuntimeError("DepthProjector: confidence must be a contiguous fp32 tensor on %s (got %s, %s, contiguous=%s)"
+                         % (self._depth.device, confidence.dtype, confidence.device, confidence.is_contiguous()))
+    if conf_min != conf_min:
+      raise ValueError("DepthProjector: conf_min is NaN")
+    return shape[1:]
+
+  def _run(self, disp, left_img, depth, xyz, table, confidence=None, conf_min=None):
     b = self._check(disp, left_img)
+    coarse = self._check_confidence(b, confidence, conf_min)
+    outs = (nat.ptr(self._depth) if depth else None, nat.ptr(self._xyz) if xyz else None, self.voxel_size,
+            nat.ptr(self._table) if table else None, self.slots)
     with torch.cuda.device(self.device):                    # the current stream of the projector's device, not the caller's
-      nat.call("as_disp_to_points", nat.ptr(disp), nat.ptr(left_img), b, self.H, self.W, self.s, ctypes.byref(self._cam),
-               nat.ptr(self._depth) if depth else None, nat.ptr(self._xyz) if xyz else None, self.voxel_size,
-               nat.ptr(self._table) if table else None, self.slots, nat.stream())
+      if coarse is None:
+        nat.call("as_disp_to_points", nat.ptr(disp), nat.ptr(left_img), b, self.H, self.W, self.s, ctypes.byref(self._cam),
+                 *(outs + (nat.stream(),)))
+      else:
+        nat.call("as_upsample_bilinear_fwd", nat.ptr(confidence), b, coarse[0], coarse[1], nat.ptr(self._conf), self.h, self.w, 1.0,
+                 nat.stream())
+        self._conf_batch = b
+        nat.call("as_disp_to_points_gated", nat.ptr(disp), nat.ptr(left_img), nat.ptr(self._conf), float(conf_min), b, self.H,
+                 self.W, self.s, ctypes.byref(self._cam), *(outs + (nat.ptr(self._rejected), nat.stream())))
     return b
 
   def depth(self, disp):
@@ -146,14 +195,21 @@ class DepthProjector(object):
     b = self._run(disp, None, True, False, False)
     return self._depth[:b]
 
-  def organized(self, disp):
-    """(xyz [B,3,h,w] with NaN at invalid pixels, depth [B,1,h,w])."""
-    b = self._run(disp, None, True, True, False)
+  def organized(self, disp, confidence=None, conf_min=None):
+    """(xyz [B,3,h,w] with NaN at invalid pixels, depth [B,1,h,w]).  With confidence and conf_min the pixels below the gate are
+    NaN in xyz too (their depth is written as ever); ``rejected`` [B] counts them."""
+    b = self._run(disp, None, True, True, False, confidence, conf_min)
     return self._xyz[:b], self._depth[:b]
 
-  def voxel_cloud(self, disp, left_img=None):
-    """The voxel-filtered cloud of each image, coloured by left_img [B,3,H,W] in [0,1] when given."""
-    b = self._run(disp, left_img, False, False, True)
+  @property
+  def rejected(self):
+    """[B] int32: per image the pixels the last gated call found valid by depth and below conf_min."""
+    return self._rejected[:self._conf_batch]
+
+  def voxel_cloud(self, disp, left_img=None, confidence=None, conf_min=None):
+    """The voxel-filtered cloud of each image, coloured by left_img [B,3,H,W] in [0,1] when given; with confidence and conf_min,
+    of the pixels at or above the gate (VoxelCloud.rejected counts the others)."""
+    b = self._run(disp, left_img, False, False, True, confidence, conf_min)
     with torch.cuda.device(self.device):
       try:
         nat.call("as_voxel_cloud_finalize", nat.ptr(self._table), b, self.slots, self.cap, nat.ptr(self._records),
@@ -162,4 +218,5 @@ class DepthProjector(object):
         # the insert ran and nothing emptied the table: clear it, or the next frame would see this one's voxels
         nat.call("as_voxel_table_clear", nat.ptr(self._table), self.B, self.slots, nat.stream())
         raise
-    return VoxelCloud(b, self._records, self._voxel, self._count, self._n, self._dropped)
+    return VoxelCloud(b, self._records, self._voxel, self._count, self._n, self._dropped,
+                      None if confidence is None else self._rejected)

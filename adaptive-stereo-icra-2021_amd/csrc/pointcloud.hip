@@ -10,7 +10,9 @@
 //   pointcloud_kernel   one lane per output pixel, lanes along a row: 2x2 mean of the disparity (and colour), depth, quantised
 //                       z, x and y, the three voxel indices as one 64-bit key, then the insert into the image's open-addressing
 //                       table: atomicCAS on the key (linear probing, at most `slots` probes), 64-bit adds of the coordinates in
-//                       2^-16 m, 32-bit adds of the count and the colour.
+//                       2^-16 m, 32-bit adds of the count and the colour.  pointcloud_kernel<true> (as_disp_to_points_gated) is the
+//                       same code with one more load and compare per pixel: a confidence below conf_min takes the pixel out
+//                       before the index-range check, and the pixels taken out are counted per image (a ballot, one add per wave).
 //   finalize_kernel     one lane per slot: occupied slots are compacted into records (one 16-byte store each), one counter add
 //                       per wave; every slot it read as occupied is handed back empty, so the next frame starts clean.
 //
@@ -93,9 +95,13 @@ __device__ inline void pc_insert(const PcTable& t, uint32_t mask, u64 key, const
   atomicAdd(t.dropped, a.cr >> 16);
 }
 
+// GATED: a pixel valid by the depth rules is kept only when conf[b][v][u] >= conf_min (false for a NaN); the ones that fail are
+// counted per image, one counter add per wave from a ballot.  Without the flag the code is what it was before the gate existed.
+template <bool GATED>
 __global__ __launch_bounds__(256) void pointcloud_kernel(const float* __restrict__ disp, const float* __restrict__ rgb, PcParams P,
                                                          float* __restrict__ depth_out, float* __restrict__ xyz_out, void* table,
-                                                         long slots) {
+                                                         long slots, const float* __restrict__ conf, float conf_min,
+                                                         int* __restrict__ rejected) {
   const int b = blockIdx.y;
   const int idx = blockIdx.x * 256 + threadIdx.x;
   const int hw = P.h * P.w;
@@ -120,6 +126,13 @@ __global__ __launch_bounds__(256) void pointcloud_kernel(const float* __restrict
     valid = z > 0.f && z <= P.depth_trunc;
   }
   valid = valid && inside;
+  if (GATED) {
+    const float c = inside ? conf[(long)b * hw + idx] : 0.f;
+    const bool pass = c >= conf_min;                    // false for NaN
+    const u64 failed = __ballot(valid && !pass);
+    if (rejected && failed && (threadIdx.x & 63) == __ffsll((long long)failed) - 1) atomicAdd(rejected + b, __popcll(failed));
+    valid = valid && pass;
+  }
   const float x = (((float)u - P.cxs) * z) / P.fxs;
   const float y = (((float)v - P.cys) * z) / P.fys;
 
@@ -241,33 +254,61 @@ extern "C" int as_voxel_table_clear(void* table, int B, int64_t slots, void* str
   return AS_OK;
 }
 
-extern "C" int as_disp_to_points(const float* disp, const float* rgb, int B, int H, int W, int s, const as_depth_camera* cam,
-                                 float* depth_out, float* xyz_out, float voxel_size, void* table, int64_t slots, void* stream) {
+static int pc_disp_to_points(const char* name, const float* disp, const float* rgb, const float* conf, float conf_min, bool gated,
+                             int B, int H, int W, int s, const as_depth_camera* cam, float* depth_out, float* xyz_out,
+                             float voxel_size, void* table, int64_t slots, int32_t* rejected, void* stream) {
   AS_CHECK_ARG(disp && cam && B > 0 && B <= PC_MAX_BATCH && H > 0 && W > 0 && s >= 0 && s <= 2,
-               "as_disp_to_points: bad argument (B %d of at most %d, H %d, W %d, s %d)", B, PC_MAX_BATCH, H, W, s);
+               "%s: bad argument (B %d of at most %d, H %d, W %d, s %d)", name, B, PC_MAX_BATCH, H, W, s);
   const int h = H >> s, w = W >> s;
   AS_CHECK_ARG(h > 0 && w > 0 && (int64_t)B * 3 * H * W < ((int64_t)1 << 40) && (int64_t)H * W < ((int64_t)1 << 30),
-               "as_disp_to_points: %dx%d at scale %d has no output pixels, or the frame is too large", H, W, s);
+               "%s: %dx%d at scale %d has no output pixels, or the frame is too large", name, H, W, s);
   AS_CHECK_ARG(cam->fb == cam->fb && cam->fxs > 0.f && cam->fys > 0.f && cam->cxs == cam->cxs && cam->cys == cam->cys,
-               "as_disp_to_points: bad camera (fb %g, fxs %g, fys %g, cxs %g, cys %g)", cam->fb, cam->fxs, cam->fys, cam->cxs, cam->cys);
+               "%s: bad camera (fb %g, fxs %g, fys %g, cxs %g, cys %g)", name, cam->fb, cam->fxs, cam->fys, cam->cxs, cam->cys);
   AS_CHECK_ARG(cam->max_depth > 0.f && cam->depth_scale >= 0.f && cam->depth_trunc > 0.f &&
                (double)cam->max_depth * cam->depth_scale <= 65535.0,
-               "as_disp_to_points: max_depth %g * depth_scale %g must fit a 16-bit depth image (and depth_trunc %g be positive)",
+               "%s: max_depth %g * depth_scale %g must fit a 16-bit depth image (and depth_trunc %g be positive)", name,
                cam->max_depth, cam->depth_scale, cam->depth_trunc);
-  AS_CHECK_ARG(depth_out || xyz_out || table, "as_disp_to_points: no output requested");
+  AS_CHECK_ARG(depth_out || xyz_out || table, "%s: no output requested", name);
+  if (gated) AS_CHECK_ARG(conf && conf_min == conf_min, "%s: conf is required and conf_min %g must not be NaN", name, conf_min);
   if (table) {
-    AS_CHECK_ARG(voxel_size > 0.f && voxel_size <= PC_MAX_VOXEL, "as_disp_to_points: voxel_size %g outside (0, %g]", voxel_size,
-                 PC_MAX_VOXEL);
-    AS_CHECK_ARG(((uintptr_t)table & 15) == 0, "as_disp_to_points: the table must be 16-byte aligned");
+    AS_CHECK_ARG(voxel_size > 0.f && voxel_size <= PC_MAX_VOXEL, "%s: voxel_size %g outside (0, %g]", name, voxel_size, PC_MAX_VOXEL);
+    AS_CHECK_ARG(((uintptr_t)table & 15) == 0, "%s: the table must be 16-byte aligned", name);
     AS_CHECK_ARG(pc_slots_ok(slots) && slots >= (int64_t)h * w,
-                 "as_disp_to_points: slots %lld must be a power of two >= 64 and >= h*w = %lld", (long long)slots, (long long)h * w);
+                 "%s: slots %lld must be a power of two >= 64 and >= h*w = %lld", name, (long long)slots, (long long)h * w);
   }
   PcParams P = {H, W, h, w, s, cam->fb, cam->fxs, cam->fys, cam->cxs, cam->cys, cam->max_depth, cam->depth_scale,
                 cam->depth_trunc, voxel_size};
+  hipStream_t st = (hipStream_t)stream;
   const dim3 grid(as_div_up((long)h * w, 256), B), block(256);
-  hipLaunchKernelGGL(pointcloud_kernel, grid, block, 0, (hipStream_t)stream, disp, rgb, P, depth_out, xyz_out, table, (long)slots);
-  AS_CHECK_LAUNCH("as_disp_to_points");
+  if (gated) {
+    if (rejected) {
+      const hipError_t e = hipMemsetAsync(rejected, 0, (size_t)B * 4, st);
+      if (e != hipSuccess) {
+        as_set_error("%s: memset failed: %s", name, hipGetErrorString(e));
+        return AS_ERR_LAUNCH;
+      }
+    }
+    hipLaunchKernelGGL(pointcloud_kernel<true>, grid, block, 0, st, disp, rgb, P, depth_out, xyz_out, table, (long)slots, conf,
+                       conf_min, rejected);
+  } else {
+    hipLaunchKernelGGL(pointcloud_kernel<false>, grid, block, 0, st, disp, rgb, P, depth_out, xyz_out, table, (long)slots,
+                       (const float*)nullptr, 0.f, (int*)nullptr);
+  }
+  AS_CHECK_LAUNCH(name);
   return AS_OK;
+}
+
+extern "C" int as_disp_to_points(const float* disp, const float* rgb, int B, int H, int W, int s, const as_depth_camera* cam,
+                                 float* depth_out, float* xyz_out, float voxel_size, void* table, int64_t slots, void* stream) {
+  return pc_disp_to_points("as_disp_to_points", disp, rgb, nullptr, 0.f, false, B, H, W, s, cam, depth_out, xyz_out, voxel_size, table,
+                           slots, nullptr, stream);
+}
+
+extern "C" int as_disp_to_points_gated(const float* disp, const float* rgb, const float* conf, float conf_min, int B, int H, int W,
+                                       int s, const as_depth_camera* cam, float* depth_out, float* xyz_out, float voxel_size,
+                                       void* table, int64_t slots, int32_t* rejected, void* stream) {
+  return pc_disp_to_points("as_disp_to_points_gated", disp, rgb, conf, conf_min, true, B, H, W, s, cam, depth_out, xyz_out, voxel_size,
+                           table, slots, rejected, stream);
 }
 
 extern "C" int as_voxel_cloud_finalize(void* table, int B, int64_t slots, int cap, void* records, int32_t* voxel, int32_t* count,

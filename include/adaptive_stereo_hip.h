@@ -781,6 +781,50 @@ int as_disp_to_points(const float* disp, const float* rgb, int B, int H, int W, 
                       float* depth_out, float* xyz_out, float voxel_size, void* table, int64_t slots, void* stream);
 int as_voxel_cloud_finalize(void* table, int B, int64_t slots, int cap, void* records, int32_t* voxel, int32_t* count,
                             int32_t* n, int32_t* dropped, void* stream);
+/* as_disp_to_points_gated: as_disp_to_points with a confidence gate; everything not named here is as_disp_to_points', from the
+ * same device code.  conf [B][h][w] (required, dense fp32, at the pyramid level's OWN resolution h = H >> s, w = W >> s);
+ * conf_min must not be NaN (-inf keeps every pixel with a number for a confidence).
+ *   gate      a pixel that is valid by the depth rules above is kept only when conf[b][v][u] >= conf_min (one fp32 compare; a
+ *             NaN confidence fails it, +inf passes).  A rejected pixel is NaN (0x7FC00000) in all three planes of xyz_out and
+ *             is not inserted into the table; the index-range check runs after the gate, so it is not counted in dropped[b]
+ *             either.  depth_out is written as before for EVERY pixel.
+ *   rejected  NULL or [B] int32, OVERWRITTEN: the number of pixels of image b that were valid by depth and failed the gate
+ *             (zeroed on the stream in front of the launch, then one counter add per wave from a ballot; integers: exact).
+ * Everything is enqueued on the caller's stream: allocates nothing, never waits, capturable. */
+int as_disp_to_points_gated(const float* disp, const float* rgb, const float* conf, float conf_min, int B, int H, int W, int s,
+                            const as_depth_camera* cam, float* depth_out, float* xyz_out, float voxel_size, void* table,
+                            int64_t slots, int32_t* rejected, void* stream);
+
+/* ---- per-pixel disparity confidence and binned error statistics (csrc/confidence.hip) — no counterpart in the reference ------
+ * as_disp_confidence: one launch over logits [B][D][H][W] (dense fp32, as as_softargmax_fwd reads it), 1 <= D <= 64, B <= 65535,
+ * H * W <= 2^30.  Outputs [B][H][W], each may be NULL (at least one is not).  A bad argument returns AS_ERR_ARG before any launch.
+ * No atomics, no workspace; allocates nothing, never waits, capturable.  Compiled with `#pragma clang fp contract(off)`: every
+ * expression below is a sequence of single IEEE fp32 operations in the written order.  Per pixel, x_d its D logits:
+ *   maximum   m1 and a = the maximum and the FIRST index attaining it: `if (x_d > m1) { m1 = x_d; a = d; }` over d in increasing
+ *             order from m1 = -inf, a = 0.  For finite columns the index as_softargmax_fwd's argmax gives.
+ *   exps      t_d = x_d - m1, e_d = expf(t_d), se = the sum of e_d in increasing d from 0.f: as_softargmax_fwd's se.
+ *   pmax      1.f / se: the soft-max probability of the mode.
+ *   mass      ((e_{a-1} + e_a) + e_{a+1}) / se, a neighbour outside [0, D) contributing 0.f: the probability within one coarse
+ *             disparity of the mode.
+ *   cent      1.f - Hn / logf((float)D), then fminf(fmaxf(., 0.f), 1.f); Hn = logf(se) - T / se; T = the sum in increasing d
+ *             from 0.f of (e_d == 0.f ? 0.f : e_d * t_d), each product rounded on its own.  One minus the normalised entropy.
+ *   D == 1    all three maps are 1.f.
+ *   bad       a column holding a NaN or a +inf, or consisting only of -inf, is the quiet NaN 0x7FC00000 in every map (for every
+ *             D, 1 included).  A -inf among finite values is legal: probability 0.
+ *
+ * as_sparsification: error statistics of pred against gt, binned by a key map.  key, pred, gt: n fp32 elements each, any shape;
+ * 1 <= n <= 2^40, 1 <= K <= 1024, lo finite, scale positive and finite (the caller's float(K / (hi - lo)), rounded once on the
+ * host), tau not NaN; count [K], bad [K], skipped [1] int64 and abs_err [K] fp64, 8-byte aligned.  Per element, in fp32:
+ *   !(gt > 0)            ignored, as in as_eval_metrics.
+ *   err = fabsf(pred - gt).  key or err NaN: *skipped += 1 and nothing else.
+ *   t = (key - lo) * scale (two single operations); k = t < 0 ? 0 : (t >= (float)K ? K - 1 : (int)t).
+ *   count[k] += 1;  bad[k] += err > tau;  abs_err[k] += (double)err.
+ * All four outputs ACCUMULATE (the caller zeroes them): batches add up, and a captured call appends on every replay.  The
+ * integers are exact.  abs_err is an fp64 sum in an unspecified order (per-workgroup partial sums, then atomics): it differs
+ * from the exact sum by at most n 2^-53 times the bin's sum.  Allocates nothing, never waits, capturable. */
+int as_disp_confidence(const float* logits, int B, int D, int H, int W, float* pmax, float* cent, float* mass, void* stream);
+int as_sparsification(const float* key, const float* pred, const float* gt, int64_t n, float lo, float scale, int K, float tau,
+                      int64_t* count, int64_t* bad, double* abs_err, int64_t* skipped, void* stream);
 
 /* ---- per-image feature-contrast scores (csrc/ood.hip) — evaluation/ood_analysis.py:76-77, utils/feature_contrast.py ------
  * One pass over logits [B][D][H][W] (dense fp32, as as_softargmax_fwd reads it), 1 <= D <= 64 (more: AS_ERR_ARG before any

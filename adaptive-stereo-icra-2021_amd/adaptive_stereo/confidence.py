@@ -22,16 +22,14 @@ import numpy as np
 import torch
 
 from . import _native as nat
+from .collect import check_f32
 
 KINDS = ("pmax", "entropy", "mass", "fcs")
 MAX_BINS = 1024
 
 
 def _check_volume(cost_volume):
-  nat.require_gpu(cost_volume)
-  if cost_volume.dim() != 4 or cost_volume.dtype != torch.float32 or not cost_volume.is_contiguous():
-    raise RuntimeError("adaptive_stereo.confidence: expected a contiguous fp32 [B,D,H,W] tensor on the GPU (got %s, %s, "
-                       "contiguous=%s)" % (tuple(cost_volume.shape), cost_volume.dtype, cost_volume.is_contiguous()))
+  check_f32("adaptive_stereo.confidence", "cost_volume", cost_volume, ((4,), "[B,D,H,W]"))
   return cost_volume.detach()
 
 
@@ -115,12 +113,7 @@ class SparsificationCollector(object):
     graph every replay adds."""
     n = key.numel()
     for name, t in (("key", key), ("pred", pred), ("gt", gt)):
-      if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError("adaptive_stereo: tensors must live on the GPU (got %s for %s); there is no CPU path"
-                           % (getattr(t, "device", type(t)), name))
-      if t.dtype != torch.float32 or not t.is_contiguous() or t.device != self._err.device or t.numel() != n:
-        raise RuntimeError("SparsificationCollector.add: %s must be a contiguous fp32 tensor of %d elements on %s (got %s, %s, %s, "
-                           "contiguous=%s)" % (name, n, self._err.device, tuple(t.shape), t.dtype, t.device, t.is_contiguous()))
+      check_f32("SparsificationCollector.add", name, t, device=self._err.device, numel=n)
     if n < 1:
       raise RuntimeError("SparsificationCollector.add: empty input")
     K = self.bins

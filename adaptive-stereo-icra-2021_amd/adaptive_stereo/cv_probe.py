@@ -15,9 +15,12 @@ the OOD gate itself uses (as_fcs_scores' mean map, bit for bit).
 Rules: an image holding a NaN selects its first NaN pixel both times (d_max -1, max / mean_rest NaN, profile all NaN); for D <= 2
 the map is 0 everywhere, so both picks are pixel 0 and mean_rest is NaN.
 """
+import contextlib
+
 import torch
 
 from . import _native as nat
+from .collect import RowCursor, check_f32, eval_batches
 
 HI, LO = 0, 1          # index of the second axis: the pixel where the map is largest / smallest
 
@@ -83,36 +86,26 @@ def probe_cost_volume(cost_volume, gt=None, profile=False):
   return ProbeResult(pix, vals, slices, prof)
 
 
-class CostVolumeProbe(object):
+class CostVolumeProbe(RowCursor):
   """Row buffers for `capacity` images of D disparities on the device, with their cursor and a counter of the rows that did not
   fit, allocated once."""
 
   def __init__(self, capacity, D, profile=False, device="cuda"):
-    self.capacity, self.D = int(capacity), int(D)
-    if self.capacity < 1:
-      raise ValueError("CostVolumeProbe: capacity %r must be at least 1" % (capacity,))
+    self.D = int(D)
     if not (1 <= self.D <= 64):
       raise ValueError("CostVolumeProbe: D %r outside [1, 64]" % (D,))
-    dev = torch.device(device)
-    if dev.type != "cuda":
-      raise RuntimeError("adaptive_stereo: CostVolumeProbe lives on the GPU (got %s); there is no CPU path" % dev)
-    self.device = dev
+    super().__init__("CostVolumeProbe", capacity, device)
+    dev = self.device
     self._pix = torch.zeros(self.capacity, 2, 3, dtype=torch.int32, device=dev)
     self._vals = torch.zeros(self.capacity, 2, 5, dtype=torch.float32, device=dev)
     self._slices = torch.zeros(self.capacity, 2, self.D, dtype=torch.float32, device=dev)
     self._profile = torch.zeros(self.capacity, self.D, dtype=torch.float32, device=dev) if profile else None
-    self._state = torch.zeros(2, dtype=torch.int32, device=dev)          # cursor, dropped
-    self._cursor, self._dropped = self._state[0:1], self._state[1:2]
 
   def add(self, cost_volume, gt=None):
     """Appends the B rows of a contiguous fp32 volume [B,D,H,W] at the cursor.  Allocates nothing and never synchronises; inside
     a captured graph every replay appends.  Rows beyond the capacity are counted in dropped()."""
-    nat.require_gpu(cost_volume, gt)
-    if cost_volume.dim() != 4 or cost_volume.dtype != torch.float32 or not cost_volume.is_contiguous() or \
-       cost_volume.device != self._pix.device:
-      raise RuntimeError("CostVolumeProbe.add: expected a contiguous fp32 [B,D,H,W] tensor on %s (got %s, %s, %s, contiguous=%s)"
-                         % (self._pix.device, tuple(cost_volume.shape), cost_volume.dtype, cost_volume.device,
-                            cost_volume.is_contiguous()))
+    check_f32("CostVolumeProbe.add", "cost_volume", cost_volume, ((4,), "[B,D,H,W]"), self._pix.device)
+    nat.require_gpu(gt)
     B, D, H, W = cost_volume.shape
     if D != self.D:
       raise RuntimeError("CostVolumeProbe.add: the volume has D %d, the buffers were allocated for D %d" % (D, self.D))
@@ -124,55 +117,32 @@ class CostVolumeProbe(object):
 
   def results(self):
     """Synchronises.  The rows in use as a ProbeResult (clones: later add() calls do not change them)."""
-    n = min(int(self._state[0]), self.capacity)
+    n = self.rows_in_use()
     return ProbeResult(self._pix[:n].clone(), self._vals[:n].clone(), self._slices[:n].clone(),
                        None if self._profile is None else self._profile[:n].clone())
-
-  def dropped(self):
-    """Synchronises.  How many rows did not fit since the last reset()."""
-    return int(self._state[1])
-
-  def reset(self):
-    self._state.zero_()
 
 
 def collect_probes(feature_net, stereo_net, batches, num_images, input_scale=0, profile=False, on_batch=None):
   """ProbeResult of n <= num_images images of the left cost volume over `batches`, any iterable of dicts with ``color_l/{s}``,
-  ``color_r/{s}`` and, when it is there, ``gt_disp_l/{s+k}``: eval mode, no_grad, forward with output_cost_volume=True,
-  CostVolumeProbe.add (the compute of the reference's save_cost_volumes and of the numbers in visualize_cost_volumes,
-  cost_volume_analysis.py:34-92).  Stops once num_images rows are in; one read-back, at the end.  Each network's train/eval state
-  is restored.  ``on_batch(first_index, cost_volume, gt)`` is called per batch with the device tensors (gt may be None)."""
-  s = int(input_scale)
-  key = "cost_volume_l/{}".format(s + stereo_net.k)
-  gt_key = "gt_disp_l/{}".format(s + stereo_net.k)
-  f_training, s_training = feature_net.training, stereo_net.training
-  feature_net.eval(); stereo_net.eval()
-  probe, seen = None, 0
-  try:
-    with torch.no_grad():
-      for inputs in batches:
-        if seen >= num_images:
-          break
-        left = inputs["color_l/{}".format(s)].cuda()
-        right = inputs["color_r/{}".format(s)].cuda()
-        if left.shape == right.shape:                      # eval-mode features are batch-independent: one pass for both images
-          both = feature_net(torch.cat([left, right]))
-          left_feat, right_feat = both[:left.shape[0]], both[left.shape[0]:]
-        else:
-          left_feat, right_feat = feature_net(left), feature_net(right)
-        outputs = stereo_net(left, left_feat, right_feat, "l", output_cost_volume=True)
-        logits = nat.f32c(outputs[key].detach())
-        gt = nat.f32c(inputs[gt_key].cuda()) if gt_key in inputs else None
-        if gt is not None and gt.dim() == 3:
-          gt = gt.unsqueeze(1)
-        if probe is None:
-          probe = CostVolumeProbe(num_images, logits.shape[1], profile=profile, device=logits.device)
-        probe.add(logits, gt)
-        if on_batch is not None:
-          on_batch(seen, logits, gt)
-        seen += left.shape[0]
-  finally:
-    feature_net.train(f_training); stereo_net.train(s_training)
+  ``color_r/{s}`` and, when it is there, ``gt_disp_l/{s+k}``: collect.eval_batches (eval mode, no_grad, forward with
+  output_cost_volume=True), CostVolumeProbe.add (the compute of the reference's save_cost_volumes and of the numbers in
+  visualize_cost_volumes, cost_volume_analysis.py:34-92).  Stops once num_images rows are in; one read-back, at the end.  Each
+  network's train/eval state is restored.  ``on_batch(first_index, cost_volume, gt)`` is called per batch with the device
+  tensors (gt may be None)."""
+  key = "cost_volume_l/{}".format(int(input_scale) + stereo_net.k)
+  gt_key = "gt_disp_l/{}".format(int(input_scale) + stereo_net.k)
+  probe = None
+  with torch.no_grad(), contextlib.closing(eval_batches(feature_net, stereo_net, batches, num_images, input_scale)) as passes:
+    for first, inputs, _, outputs in passes:
+      logits = nat.f32c(outputs[key].detach())
+      gt = nat.f32c(inputs[gt_key].cuda()) if gt_key in inputs else None
+      if gt is not None and gt.dim() == 3:
+        gt = gt.unsqueeze(1)
+      if probe is None:
+        probe = CostVolumeProbe(num_images, logits.shape[1], profile=profile, device=logits.device)
+      probe.add(logits, gt)
+      if on_batch is not None:
+        on_batch(first, logits, gt)
   if probe is None:
     return ProbeResult(torch.zeros(0, 2, 3, dtype=torch.int32), torch.zeros(0, 2, 5), torch.zeros(0, 2, 0),
                        torch.zeros(0, 0) if profile else None)

@@ -13,6 +13,7 @@ to the caller: every function returns the numbers a plot would show.
   train = collector.scores()[:, 0]                        # synchronises; column 0 max-minus-mean, column 1 max-minus-median
   threshold, mu, sigma = ood_threshold(train, 0.05)       # --ood_threshold
 """
+import contextlib
 import math
 import statistics
 
@@ -20,6 +21,7 @@ import numpy as np
 import torch
 
 from . import _native as nat
+from .collect import RowCursor, check_f32, eval_batches
 
 
 def _logits(cost_volume):
@@ -48,30 +50,17 @@ def fcs_scores(cost_volume, maps=False):
   return (scores, fmean, fmed) if maps else scores
 
 
-class FcsCollector(object):
+class FcsCollector(RowCursor):
   """A [capacity,2] score buffer on the device with its cursor and a counter of the rows that did not fit, allocated once."""
 
   def __init__(self, capacity, device="cuda"):
-    self.capacity = int(capacity)
-    if self.capacity < 1:
-      raise ValueError("FcsCollector: capacity %r must be at least 1" % (capacity,))
-    dev = torch.device(device)
-    if dev.type != "cuda":
-      raise RuntimeError("adaptive_stereo: FcsCollector lives on the GPU (got %s); there is no CPU path" % dev)
-    self.device = dev
-    self._scores = torch.zeros(self.capacity, 2, dtype=torch.float32, device=dev)
-    self._state = torch.zeros(2, dtype=torch.int32, device=dev)          # cursor, dropped
-    self._cursor, self._dropped = self._state[0:1], self._state[1:2]
+    super().__init__("FcsCollector", capacity, device)
+    self._scores = torch.zeros(self.capacity, 2, dtype=torch.float32, device=self.device)
 
   def add(self, cost_volume):
     """Appends the B rows of a contiguous fp32 volume [B,D,H,W] at the cursor.  Allocates nothing and never synchronises; inside
     a captured graph every replay appends.  Rows beyond the capacity are counted in dropped()."""
-    nat.require_gpu(cost_volume)
-    if cost_volume.dim() != 4 or cost_volume.dtype != torch.float32 or not cost_volume.is_contiguous() or \
-       cost_volume.device != self._scores.device:
-      raise RuntimeError("FcsCollector.add: expected a contiguous fp32 [B,D,H,W] tensor on %s (got %s, %s, %s, contiguous=%s)"
-                         % (self._scores.device, tuple(cost_volume.shape), cost_volume.dtype, cost_volume.device,
-                            cost_volume.is_contiguous()))
+    check_f32("FcsCollector.add", "cost_volume", cost_volume, ((4,), "[B,D,H,W]"), self._scores.device)
     B, D, H, W = cost_volume.shape
     with torch.cuda.device(self.device):
       nat.call("as_fcs_scores", nat.ptr(cost_volume), B, D, H, W, None, None, nat.ptr(self._scores), self.capacity,
@@ -79,46 +68,21 @@ class FcsCollector(object):
 
   def scores(self):
     """Synchronises.  The rows in use, [n,2] (a clone: later add() calls do not change it)."""
-    n = min(int(self._state[0]), self.capacity)
-    return self._scores[:n].clone()
-
-  def dropped(self):
-    """Synchronises.  How many rows did not fit since the last reset()."""
-    return int(self._state[1])
-
-  def reset(self):
-    self._state.zero_()
+    return self._scores[:self.rows_in_use()].clone()
 
 
 def collect_scores(feature_net, stereo_net, batches, num_images, input_scale=0):
   """Scores [n,2] (n <= num_images) of the left cost volume over `batches`, any iterable of dicts with ``color_l/{s}`` and
-  ``color_r/{s}``: eval mode, no_grad, forward with output_cost_volume=True, FcsCollector.add (the compute of the reference's
-  save_data, ood_analysis.py:40-90).  Stops once num_images rows are in; one read-back, at the end.  Each network's
-  train/eval state is restored."""
-  s = int(input_scale)
-  key = "cost_volume_l/{}".format(s + stereo_net.k)
-  f_training, s_training = feature_net.training, stereo_net.training
-  feature_net.eval(); stereo_net.eval()
-  collector, seen = None, 0
-  try:
-    with torch.no_grad():
-      for inputs in batches:
-        if seen >= num_images:
-          break
-        left = inputs["color_l/{}".format(s)].cuda()
-        right = inputs["color_r/{}".format(s)].cuda()
-        if collector is None:
-          collector = FcsCollector(num_images, device=left.device)
-        if left.shape == right.shape:                      # eval-mode features are batch-independent: one pass for both images
-          both = feature_net(torch.cat([left, right]))
-          left_feat, right_feat = both[:left.shape[0]], both[left.shape[0]:]
-        else:
-          left_feat, right_feat = feature_net(left), feature_net(right)
-        outputs = stereo_net(left, left_feat, right_feat, "l", output_cost_volume=True)
-        collector.add(nat.f32c(outputs[key].detach()))
-        seen += left.shape[0]
-  finally:
-    feature_net.train(f_training); stereo_net.train(s_training)
+  ``color_r/{s}``: collect.eval_batches (eval mode, no_grad, forward with output_cost_volume=True), FcsCollector.add (the
+  compute of the reference's save_data, ood_analysis.py:40-90).  Stops once num_images rows are in; one read-back, at the end.
+  Each network's train/eval state is restored."""
+  key = "cost_volume_l/{}".format(int(input_scale) + stereo_net.k)
+  collector = None
+  with torch.no_grad(), contextlib.closing(eval_batches(feature_net, stereo_net, batches, num_images, input_scale)) as passes:
+    for _, _, left, outputs in passes:
+      if collector is None:
+        collector = FcsCollector(num_images, device=left.device)
+      collector.add(nat.f32c(outputs[key].detach()))
   if collector is None:
     return torch.zeros(0, 2, dtype=torch.float32)
   return collector.scores()

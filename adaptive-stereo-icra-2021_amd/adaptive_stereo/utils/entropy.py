@@ -12,6 +12,7 @@ fp64 (the arithmetic is a contract: include/adaptive_stereo_hip.h).  A per-image
 import torch
 
 from .. import _native as nat
+from ..collect import RowCursor, check_f32
 
 __all__ = ["grayscale_shannon_entropy", "gradient_shannon_entropy", "image_entropy", "EntropyCollector", "release_workspaces"]
 
@@ -99,33 +100,22 @@ def gradient_shannon_entropy(img):
   return _single(img, "gradient_shannon_entropy")[1]
 
 
-class EntropyCollector(object):
-  """A [capacity,2] score buffer on the device with its cursor and a counter of the rows that did not fit, allocated once: the
-  twin of ood.FcsCollector for image_entropy's two columns."""
+class EntropyCollector(RowCursor):
+  """A [capacity,2] score buffer on the device with its cursor and a counter of the rows that did not fit, allocated once:
+  ood.FcsCollector for image_entropy's two columns."""
 
   def __init__(self, capacity, device="cuda"):
-    self.capacity = int(capacity)
-    if self.capacity < 1:
-      raise ValueError("EntropyCollector: capacity %r must be at least 1" % (capacity,))
-    dev = torch.device(device)
-    if dev.type != "cuda":
-      raise RuntimeError("adaptive_stereo: EntropyCollector lives on the GPU (got %s); there is no CPU path" % dev)
-    self.device = dev
-    self._scores = torch.zeros(self.capacity, 2, dtype=torch.float32, device=dev)
-    self._state = torch.zeros(2, dtype=torch.int32, device=dev)          # cursor, dropped
-    self._cursor, self._dropped = self._state[0:1], self._state[1:2]
+    super().__init__("EntropyCollector", capacity, device)
+    self._scores = torch.zeros(self.capacity, 2, dtype=torch.float32, device=self.device)
     self._workspace = None                                               # sized by the first add()
 
   def add(self, images):
     """Appends the B rows of a contiguous fp32 batch [B,C,H,W] or [B,H,W] at the cursor.  After the first call (which sizes the
     workspace) it allocates nothing and never synchronises; inside a captured graph every replay appends.  Rows beyond the
     capacity are counted in dropped()."""
-    nat.require_gpu(images)
-    if images.dim() not in (3, 4) or images.dtype != torch.float32 or not images.is_contiguous() or \
-       images.device != self._scores.device or images.numel() == 0:
-      raise RuntimeError("EntropyCollector.add: expected a contiguous fp32 [B,C,H,W] or [B,H,W] tensor on %s (got %s, %s, %s, "
-                         "contiguous=%s)" % (self._scores.device, tuple(images.shape), images.dtype, images.device,
-                                             images.is_contiguous()))
+    check_f32("EntropyCollector.add", "images", images, ((3, 4), "[B,C,H,W] or [B,H,W]"), self._scores.device)
+    if images.numel() == 0:
+      raise RuntimeError("EntropyCollector.add: images is empty (shape %s)" % (tuple(images.shape),))
     x = images if images.dim() == 4 else images[:, None]
     need = _workspace_bytes(x.shape[0])
     if self._workspace is None or self._workspace.numel() < need:
@@ -137,12 +127,4 @@ class EntropyCollector(object):
 
   def scores(self):
     """Synchronises.  The rows in use, [n,2] (a clone: later add() calls do not change it)."""
-    n = min(int(self._state[0]), self.capacity)
-    return self._scores[:n].clone()
-
-  def dropped(self):
-    """Synchronises.  How many rows did not fit since the last reset()."""
-    return int(self._state[1])
-
-  def reset(self):
-    self._state.zero_()
+    return self._scores[:self.rows_in_use()].clone()

@@ -24,6 +24,7 @@
 //         workgroup, bn_merge.h); IN 0: x is already activated.
 #include "as_common.h"
 #include "bn_merge.h"
+#include "column_stats.h"
 
 struct TailArgs {
   const float* x;
@@ -185,7 +186,7 @@ __global__ __launch_bounds__(256, NK > 8 ? 1 : 2) void agg_tail_kernel(TailArgs 
     const int d = c4 + 8 * k;
     l[k] = d < D ? lg[d * 32 + pl] : -INFINITY;
     if (d < D && interior) p.logits[(((long)b * D + d) * p.g.H + y) * p.g.W + x] = l[k];
-    if (d < D) {
+    if (d < D) {                                           // column_stats.h's col_top2_step, written out (see there)
       sum += l[k];
       if (l[k] > m1) { m2 = m1; m1 = l[k]; am = d; }
       else if (l[k] > m2) { m2 = l[k]; }
@@ -215,7 +216,7 @@ __global__ __launch_bounds__(256, NK > 8 ? 1 : 2) void agg_tail_kernel(TailArgs 
     const long i = ((long)b * p.g.H + y) * p.g.W + x;
     p.pred[i] = acc;
     if (p.argmax) p.argmax[i] = am;
-    if (p.fcs) p.fcs[i] = (D > 2) ? m1 - (sum - m1 - m2) / (float)(D - 2) : 0.f;
+    if (p.fcs) p.fcs[i] = col_fcs(m1, m2, sum, D);
   }
 }
 
@@ -344,7 +345,7 @@ __global__ __launch_bounds__(8 * NPOS, 1) void agg_tail_direct_kernel(TailArgs p
     const int d = c4 + 8 * k;
     l[k] = d < D ? lg[d * NPOS + pl] : -INFINITY;
     if (d < D && interior) p.logits[(((long)b * D + d) * p.g.H + y) * p.g.W + x] = l[k];
-    if (d < D) {
+    if (d < D) {                                           // column_stats.h's col_top2_step, written out (see there)
       sum += l[k];
       if (l[k] > m1) { m2 = m1; m1 = l[k]; am = d; }
       else if (l[k] > m2) { m2 = l[k]; }
@@ -373,7 +374,7 @@ __global__ __launch_bounds__(8 * NPOS, 1) void agg_tail_direct_kernel(TailArgs p
     const long i = ((long)b * p.g.H + y) * p.g.W + x;
     p.pred[i] = acc;
     if (p.argmax) p.argmax[i] = am;
-    if (p.fcs) p.fcs[i] = (D > 2) ? m1 - (sum - m1 - m2) / (float)(D - 2) : 0.f;
+    if (p.fcs) p.fcs[i] = col_fcs(m1, m2, sum, D);
   }
 }
 

@@ -16,8 +16,9 @@ void as_set_error(const char* fmt, ...);
 // db[o] (+)= sum_chunks partial_db[chunk][o]; recorded instead of launched while a deferral region is open (as_wgrad_defer)
 void as_wgrad_reduce_enqueue(hipStream_t st, const float* partial, const float* partial_db, int nchunks, int T, float* dW,
                              float* db, int accumulate);
-// the one-lane launch behind a collector kernel (ood.hip): *dropped += the rows of [*cursor, *cursor + B) at or beyond capacity,
-// *cursor += B (saturating); either pointer may be NULL
+// the one-lane launch behind a collector kernel (cursor.hip): *dropped += the rows of [*cursor, *cursor + B) at or beyond capacity,
+// *cursor += B (saturating); either pointer may be NULL.  1 <= B <= AS_CURSOR_MAX_BATCH keeps cursor + b inside int32.
+#define AS_CURSOR_MAX_BATCH 65535
 void as_cursor_advance_enqueue(hipStream_t st, int32_t* cursor, int32_t* dropped, int B, int capacity);
 // measurement hook (optim.hip): event pair around a kernel launch; no-ops unless enabled
 void as_prof_mark(int kernel_id, hipStream_t st, int begin, double flops);

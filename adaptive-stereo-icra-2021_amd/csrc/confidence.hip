@@ -8,19 +8,17 @@
 // is a sequence of single IEEE operations in the written order, so nothing here may contract into an fma.
 //
 //   disp_confidence_kernel<DMAX>  one lane per coarse pixel, lanes along W, grid ceil(H*W/256) x B: each of a pixel's D loads is a
-//                                 coalesced row across the wave.  All D loads are issued before the first compare and the D values
-//                                 stay in registers (DMAX = 4 / 12 / 24 / 64, as ood.hip).  No atomics, no workspace, no LDS.  It is a
-//                                 latency-bound launch over a few hundred kilobytes and needs no tuning beyond that.
+//                                 coalesced row across the wave.  The load and the arg-max pass are column_stats.h's (col_load,
+//                                 col_top2; DMAX = 4 / 12 / 24 / 64).  No atomics, no workspace, no LDS.  It is a latency-bound
+//                                 launch over a few hundred kilobytes and needs no tuning beyond that.
 //   sparsification_kernel         grid-stride over the n elements; every workgroup keeps count / bad / abs_err of the K bins in LDS
 //                                 (integer and fp64 LDS atomics), then adds its non-empty bins to the global arrays: one 64-bit
 //                                 integer add each for count and bad, one fp64 add for abs_err.  The integers are exact in any
 //                                 order; the fp64 sum is order-dependent in its last bits (bound: n 2^-53 times the bin's sum).
-#include "as_common.h"
+#include "column_stats.h"
 
 #pragma clang fp contract(off)
 
-#define CONF_MAX_D 64
-#define CONF_MAX_BATCH 65535          // images are the grid's y dimension
 #define SP_MAX_K 1024
 #define SP_THREADS 256
 #define SP_MAX_BLOCKS 512
@@ -36,21 +34,12 @@ __global__ __launch_bounds__(256) void disp_confidence_kernel(const float* __res
   if (pix >= HW) return;
   const float* l = logits + (long)b * D * HW + pix;
   float v[DMAX];
-#pragma unroll
-  for (int d = 0; d < DMAX; ++d) v[d] = d < D ? l[(long)d * HW] : -INFINITY;
-
-  float m1 = -INFINITY;
-  int a = 0;
-  bool bad = false;
-#pragma unroll
-  for (int d = 0; d < DMAX; ++d) {
-    if (d < D) {
-      const float x = v[d];
-      if (x > m1) { m1 = x; a = d; }
-      bad = bad || x != x || x == INFINITY;
-    }
-  }
-  bad = bad || m1 == -INFINITY;                           // nothing but -inf
+  col_load<DMAX>(v, l, D, HW, -INFINITY);
+  const ColTop2 st = col_top2<DMAX>(v, D);                // the mode and where it is first reached
+  const float m1 = st.m1;
+  const int a = st.am;
+  // a NaN, a +inf (without a NaN it is the maximum) or nothing but -inf
+  const bool bad = st.has_nan || m1 == INFINITY || m1 == -INFINITY;
 
   float se = 0.f, T = 0.f, e_lo = 0.f, e_at = 0.f, e_hi = 0.f;
 #pragma unroll
@@ -127,22 +116,14 @@ __global__ __launch_bounds__(SP_THREADS) void sparsification_kernel(const float*
 
 extern "C" int as_disp_confidence(const float* logits, int B, int D, int H, int W, float* pmax, float* cent, float* mass,
                                   void* stream) {
-  AS_CHECK_ARG(logits && B > 0 && B <= CONF_MAX_BATCH && H > 0 && W > 0 && (int64_t)H * W <= ((int64_t)1 << 30),
-               "as_disp_confidence: bad argument (B %d of at most %d, H %d, W %d)", B, CONF_MAX_BATCH, H, W);
-  AS_CHECK_ARG(D >= 1 && D <= CONF_MAX_D, "as_disp_confidence: D %d outside [1, %d] (the D values of a pixel stay in registers)", D,
-               CONF_MAX_D);
+  if (int e = as_check_volume("as_disp_confidence", logits, B, D, H, W)) return e;
   AS_CHECK_ARG(pmax || cent || mass, "as_disp_confidence: no output requested");
   hipStream_t st = (hipStream_t)stream;
   const int HW = H * W;
-  const dim3 grid(as_div_up(HW, 256), B), block(256);
-  if (D <= 4)
-    hipLaunchKernelGGL(disp_confidence_kernel<4>, grid, block, 0, st, logits, D, HW, pmax, cent, mass);
-  else if (D <= 12)
-    hipLaunchKernelGGL(disp_confidence_kernel<12>, grid, block, 0, st, logits, D, HW, pmax, cent, mass);
-  else if (D <= 24)
-    hipLaunchKernelGGL(disp_confidence_kernel<24>, grid, block, 0, st, logits, D, HW, pmax, cent, mass);
-  else
-    hipLaunchKernelGGL(disp_confidence_kernel<64>, grid, block, 0, st, logits, D, HW, pmax, cent, mass);
+  as_col_dispatch(D, [&](auto dmax) {
+    hipLaunchKernelGGL(disp_confidence_kernel<decltype(dmax)::value>, dim3(as_div_up(HW, 256), B), dim3(256), 0, st, logits, D, HW,
+                       pmax, cent, mass);
+  });
   AS_CHECK_LAUNCH("as_disp_confidence");
   return AS_OK;
 }

@@ -4,31 +4,29 @@
 // torch.sort, sorted[0], sorted[2:].mean(), the ground truth there), in one launch that never leaves the device.
 //
 // The arithmetic is a CONTRACT (include/adaptive_stereo_hip.h, restated by tests/cv_probe_ref.py):
-//   map f      exactly fcs_scores_kernel's mean map (ood.hip): the same loop over d in increasing order, the same expression.
+//   map f      fcs_scores_kernel's mean map (ood.hip): column_stats.h's loop and expression, called here, written out there.
 //   selection  torch's argmax / argmin of the flattened map: the first NaN pixel if there is one, else the smallest p holding the
 //              extreme.  Every candidate is ONE 64-bit unsigned key, (order(f) << 32) | (0xFFFFFFFF - p): order() maps fp32 values
 //              to integers of the same order (-0 and +0 to the same one, NaN to the top; complemented for the minimum), so the
 //              unsigned maximum of the keys is the extreme value at the smallest p.  A maximum is associative and commutative: the
 //              walk, the butterfly and the merge of the waves cannot disagree, and no lane number enters a comparison.
 //   values     the selected pixel's D logits are read again by D lanes (the slice), staged in LDS, and one lane per extreme runs
-//              the map's loop over them once more, which also finds d_max: the same operations, so the same f.
+//              that loop (col_top2_step) over them once more, which also finds d_max: the same code, so the same f.
 //   profile    each pixel's D values are sorted in registers by a fixed network (sort_net.h; padding -inf beyond D) and added
 //              per rank in fp64: lane t over its pixels in order, xor butterfly over the wave, the waves in order.
 //
 //   cv_probe_kernel<DMAX, PROFILE>  one workgroup of 512 lanes per image, lane t takes pixels t, t + 512, ...: each of a pixel's D
 //              loads is a coalesced row across the wave.  Without the profile the sort and the rank sums are not compiled in.
-//              Registers per lane by the compiler's report (no instance uses scratch): 25 / 40 / 58 / 101 without the profile
+//              Registers per lane by the compiler's report (no instance uses scratch): 26 / 40 / 60 / 103 without the profile
 //              and 38 / 61 / 93 / 217 with it for DMAX 4 / 12 / 24 / 64.  217 fits the 256 a lane has at two waves per SIMD,
 //              which is what 512 lanes per workgroup ask for, so the DMAX = 64 instance needs neither fewer lanes nor LDS staging.
-//   the cursor launch is ood.hip's (as_cursor_advance_enqueue).
-#include "as_common.h"
+//   the cursor launch is cursor.hip's (as_cursor_advance_enqueue).
+#include "column_stats.h"
 #include "sort_net.h"
 
 #pragma clang fp contract(off)
 
-#define CVP_MAX_D 64
 #define CVP_THREADS 512
-#define CVP_MAX_BATCH 65535
 
 // fp32 (not NaN) -> uint32 of the same order, in [0x007FFFFF, 0xFF800000]; -0.f and +0.f give the same integer
 __device__ inline uint32_t cvp_order(float f) {
@@ -67,23 +65,10 @@ __global__ __launch_bounds__(CVP_THREADS) void cv_probe_kernel(const float* __re
   for (int p = tid; p < HW; p += CVP_THREADS) {
     const float* l = vol + p;
     float v[DMAX];
-#pragma unroll
-    for (int d = 0; d < DMAX; ++d) v[d] = d < D ? l[(long)d * HW] : -INFINITY;   // the padding sorts behind every real value
-
-    // fcs_scores_kernel's loop, over the D real values
-    float m1 = -INFINITY, m2 = -INFINITY, sum = 0.f;
-    bool has_nan = false;
-#pragma unroll
-    for (int d = 0; d < DMAX; ++d) {
-      if (d < D) {
-        const float x = v[d];
-        sum += x;
-        if (x > m1) { m2 = m1; m1 = x; }
-        else if (x > m2) { m2 = x; }
-        has_nan = has_nan || x != x;
-      }
-    }
-    const float f = (D > 2) ? m1 - (sum - m1 - m2) / (float)(D - 2) : 0.f;
+    col_load<DMAX>(v, l, D, HW, -INFINITY);                 // the padding sorts behind every real value (descending)
+    const ColTop2 st = col_top2<DMAX>(v, D);
+    const bool has_nan = st.has_nan;
+    const float f = col_fcs(st.m1, st.m2, st.sum, D);
     const uint32_t o = cvp_order(f), low = 0xFFFFFFFFu - (uint32_t)p;
     best_hi = cvp_max(best_hi, ((unsigned long long)(has_nan ? 0xFFFFFFFFu : o) << 32) | low);
     best_lo = cvp_max(best_lo, ((unsigned long long)(has_nan ? 0xFFFFFFFFu : ~o) << 32) | low);
@@ -104,7 +89,7 @@ __global__ __launch_bounds__(CVP_THREADS) void cv_probe_kernel(const float* __re
   }
 
   __shared__ unsigned long long keys[2][NW];
-  __shared__ float sl[2][CVP_MAX_D];
+  __shared__ float sl[2][AS_COL_MAX_D];
   __shared__ double part[PROFILE ? DMAX : 1][NW];
   best_hi = cvp_wave_max(best_hi);
   best_lo = cvp_wave_max(best_lo);
@@ -143,22 +128,13 @@ __global__ __launch_bounds__(CVP_THREADS) void cv_probe_kernel(const float* __re
   }
   __syncthreads();
   if (which < 2 && lane == 0) {
-    float m1 = -INFINITY, m2 = -INFINITY, sum = 0.f;
-    bool has_nan = false;
-    int d_max = -1;
-    for (int d = 0; d < D; ++d) {
-      const float x = sl[which][d];
-      sum += x;
-      if (x > m1) { m2 = m1; m1 = x; d_max = d; }
-      else if (x > m2) { m2 = x; }
-      has_nan = has_nan || x != x;
-    }
-    float mean_rest = nan, f = 0.f;
-    if (D > 2) {
-      mean_rest = (sum - m1 - m2) / (float)(D - 2);
-      f = m1 - mean_rest;
-    }
-    if (has_nan) { f = nan; m1 = nan; m2 = nan; mean_rest = nan; d_max = -1; }
+    ColTop2 st;
+    st.am = -1;                                              // a column of nothing but -inf has no d_max
+    for (int d = 0; d < D; ++d) col_top2_step(st, sl[which][d], d);
+    float m1 = st.m1, m2 = st.m2, f = col_fcs(m1, m2, st.sum, D);
+    float mean_rest = D > 2 ? col_mean_rest(m1, m2, st.sum, D) : nan;
+    int d_max = st.am;
+    if (st.has_nan) { f = nan; m1 = nan; m2 = nan; mean_rest = nan; d_max = -1; }
     if (pix) {
       int32_t* o = pix + (row * 2 + which) * 3;
       o[0] = p / W; o[1] = p % W; o[2] = d_max;
@@ -185,24 +161,16 @@ static void cvp_launch(hipStream_t st, int B, const float* logits, const float* 
 
 extern "C" int as_cost_volume_probe(const float* logits, const float* gt, int B, int D, int H, int W, int32_t* pix, float* vals,
                                     float* slices, float* profile, int capacity, int32_t* cursor, int32_t* dropped, void* stream) {
-  AS_CHECK_ARG(logits && B > 0 && B <= CVP_MAX_BATCH && H > 0 && W > 0 && (int64_t)H * W <= ((int64_t)1 << 30),
-               "as_cost_volume_probe: bad argument (B %d of at most %d, H %d, W %d)", B, CVP_MAX_BATCH, H, W);
-  AS_CHECK_ARG(D >= 1 && D <= CVP_MAX_D,
-               "as_cost_volume_probe: D %d outside [1, %d] (the D values of a pixel are sorted in registers)", D, CVP_MAX_D);
+  if (int e = as_check_volume("as_cost_volume_probe", logits, B, D, H, W)) return e;
   AS_CHECK_ARG(pix || vals || slices || profile,
                "as_cost_volume_probe: no output requested (pix, vals, slices and profile are all NULL%s)",
                cursor || dropped ? "; cursor and dropped belong to the rows" : "");
   AS_CHECK_ARG(capacity >= 1, "as_cost_volume_probe: capacity %d must be at least 1", capacity);
   hipStream_t st = (hipStream_t)stream;
   const int HW = H * W;
-  if (D <= 4)
-    cvp_launch<4>(st, B, logits, gt, D, HW, W, pix, vals, slices, profile, cursor, capacity);
-  else if (D <= 12)
-    cvp_launch<12>(st, B, logits, gt, D, HW, W, pix, vals, slices, profile, cursor, capacity);
-  else if (D <= 24)
-    cvp_launch<24>(st, B, logits, gt, D, HW, W, pix, vals, slices, profile, cursor, capacity);
-  else
-    cvp_launch<64>(st, B, logits, gt, D, HW, W, pix, vals, slices, profile, cursor, capacity);
+  as_col_dispatch(D, [&](auto dmax) {
+    cvp_launch<decltype(dmax)::value>(st, B, logits, gt, D, HW, W, pix, vals, slices, profile, cursor, capacity);
+  });
   AS_CHECK_LAUNCH("as_cost_volume_probe");
   if (cursor || dropped) {
     as_cursor_advance_enqueue(st, cursor, dropped, B, capacity);

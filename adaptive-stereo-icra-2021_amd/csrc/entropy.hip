@@ -26,7 +26,7 @@
 #define ENT_THREADS 256
 #define ENT_WAVES (ENT_THREADS / 64)
 #define ENT_BINS 256
-#define ENT_MAX_BATCH 65535            // as_fcs_scores' limit (FCS_MAX_BATCH): cursor + b stays inside int32
+#define ENT_MAX_BATCH AS_CURSOR_MAX_BATCH   // cursor + b stays inside int32
 #define ENT_WG_ELEMS 8192              // elements of a strip, rounded up to whole rows
 #define ENT_DEPTH 4                    // 16-byte loads a lane has in flight
 #define ENT_WS_WORDS (2 * ENT_BINS + 1)   // per image: gray counts, gradient counts, ticket

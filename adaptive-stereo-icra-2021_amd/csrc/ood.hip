@@ -3,8 +3,11 @@
 // batch) and of the other public function of its utils/feature_contrast.py, feature_contrast_median (max - torch.median).
 //
 // The arithmetic is a CONTRACT (include/adaptive_stereo_hip.h, restated by tests/ood_ref.py):
-//   mean map    exactly softargmax_fwd_kernel's fcs (softargmax.hip): the same loop over d in increasing order, the same
-//               expression, so the same bits for finite logits.
+//   mean map    the loop and expression defined in column_stats.h, which softargmax_fwd_kernel (softargmax.hip) and
+//               cv_probe_kernel call.  Here they are WRITTEN OUT, statement for statement: every form that called the header
+//               (the whole loop, the step alone, the expression alone) gave this kernel another schedule that measured
+//               0.6 - 1.3 % slower at D = 24 (profiles/column_stats_timing.txt).  tests/test_gpu_cv_probe.py
+//               (test_the_three_fcs_maps_are_one_map) and tests/test_gpu_ood.py hold the copy to the callers bit for bit.
 //   median map  max_d - (element of rank (D-1)/2 in ascending order): two input values and one subtraction.  The element is
 //               found by counting, per value, the values that sort in front of it (smaller, or equal with a smaller d); D values
 //               stay in registers, D^2 compares, no sort through memory.
@@ -14,16 +17,12 @@
 //   fcs_scores_kernel<DMAX>  one workgroup of 512 lanes per image; lane t takes pixels t, t + 512, ... of the flattened H*W, so
 //                            each of a pixel's D loads is a coalesced row across the wave.  It is a latency-bound launch over a few
 //                            hundred kilobytes: all D loads of a pixel are issued before the first compare.
-//   fcs_advance_kernel       one lane, behind it in stream order: counts the rows that did not fit and advances the cursor.  No
-//                            workgroup of the first launch writes what another one of the same launch reads.
-#include "as_common.h"
+//   the cursor launch behind it is cursor.hip's (as_cursor_advance_enqueue).
+#include "column_stats.h"
 
 #pragma clang fp contract(off)
 
-#define FCS_MAX_D 64
 #define FCS_THREADS 512
-#define FCS_MAX_BATCH 65535           // rows of one call; keeps cursor + b inside int32 (the cursor saturates below INT32_MAX - 65535)
-#define FCS_CURSOR_MAX (2147483647 - FCS_MAX_BATCH)
 
 template <int DMAX>
 __global__ __launch_bounds__(FCS_THREADS) void fcs_scores_kernel(const float* __restrict__ logits, int D, int HW,
@@ -43,7 +42,7 @@ __global__ __launch_bounds__(FCS_THREADS) void fcs_scores_kernel(const float* __
 #pragma unroll
     for (int d = 0; d < DMAX; ++d) v[d] = d < D ? l[(long)d * HW] : INFINITY;   // the padding sorts behind every real value
 
-    // softargmax_fwd_kernel's loop, over the D real values
+    // column_stats.h's col_load, col_top2 and col_fcs, written out (see the note above)
     float m1 = -INFINITY, m2 = -INFINITY, sum = 0.f;
     bool has_nan = false;
 #pragma unroll
@@ -95,42 +94,18 @@ __global__ __launch_bounds__(FCS_THREADS) void fcs_scores_kernel(const float* __
   }
 }
 
-__global__ void fcs_advance_kernel(int32_t* cursor, int32_t* dropped, int B, int capacity) {
-  const int c = cursor ? *cursor : 0;
-  if (dropped) {
-    long over = (long)c + B - (c > capacity ? c : capacity);      // rows of [c, c + B) at or beyond capacity
-    if (c < 0) over = B;                                            // a negative cursor places no row
-    if (over > 0) *dropped = (int32_t)(*dropped > 2147483647 - over ? 2147483647 : *dropped + over);
-  }
-  if (cursor && c >= 0) *cursor = c > FCS_CURSOR_MAX - B ? FCS_CURSOR_MAX : c + B;
-}
-
-// the same cursor rule for every collector kernel of the library (entropy.hip appends its rows by it)
-void as_cursor_advance_enqueue(hipStream_t st, int32_t* cursor, int32_t* dropped, int B, int capacity) {
-  hipLaunchKernelGGL(fcs_advance_kernel, dim3(1), dim3(1), 0, st, cursor, dropped, B, capacity);
-}
-
 extern "C" int as_fcs_scores(const float* logits, int B, int D, int H, int W, float* fcs_mean, float* fcs_median, float* scores,
                              int capacity, int32_t* cursor, int32_t* dropped, void* stream) {
-  AS_CHECK_ARG(logits && B > 0 && B <= FCS_MAX_BATCH && H > 0 && W > 0 && (int64_t)H * W <= ((int64_t)1 << 30),
-               "as_fcs_scores: bad argument (B %d of at most %d, H %d, W %d)", B, FCS_MAX_BATCH, H, W);
-  AS_CHECK_ARG(D >= 1 && D <= FCS_MAX_D, "as_fcs_scores: D %d outside [1, %d] (the D values of a pixel are selected in registers)", D,
-               FCS_MAX_D);
+  if (int e = as_check_volume("as_fcs_scores", logits, B, D, H, W)) return e;
   AS_CHECK_ARG(fcs_mean || fcs_median || scores, "as_fcs_scores: no output requested");
   AS_CHECK_ARG(scores ? capacity > 0 : (!cursor && !dropped),
                "as_fcs_scores: scores needs capacity > 0 (got %d); cursor and dropped belong to scores", capacity);
   hipStream_t st = (hipStream_t)stream;
   const int HW = H * W;
-  const dim3 grid(B), block(FCS_THREADS);
-  const int32_t* cur = cursor;
-  if (D <= 4)
-    hipLaunchKernelGGL(fcs_scores_kernel<4>, grid, block, 0, st, logits, D, HW, fcs_mean, fcs_median, scores, cur, capacity);
-  else if (D <= 12)
-    hipLaunchKernelGGL(fcs_scores_kernel<12>, grid, block, 0, st, logits, D, HW, fcs_mean, fcs_median, scores, cur, capacity);
-  else if (D <= 24)
-    hipLaunchKernelGGL(fcs_scores_kernel<24>, grid, block, 0, st, logits, D, HW, fcs_mean, fcs_median, scores, cur, capacity);
-  else
-    hipLaunchKernelGGL(fcs_scores_kernel<64>, grid, block, 0, st, logits, D, HW, fcs_mean, fcs_median, scores, cur, capacity);
+  as_col_dispatch(D, [&](auto dmax) {
+    hipLaunchKernelGGL(fcs_scores_kernel<decltype(dmax)::value>, dim3(B), dim3(FCS_THREADS), 0, st, logits, D, HW, fcs_mean,
+                       fcs_median, scores, (const int32_t*)cursor, capacity);
+  });
   AS_CHECK_LAUNCH("as_fcs_scores");
   if (cursor || dropped) {
     as_cursor_advance_enqueue(st, cursor, dropped, B, capacity);

@@ -12,6 +12,7 @@
 // Soft-argmax keeps one pixel per lane (d-strided, W-coalesced reads of the logits);
 // Dc is 8..24, so the per-pixel reduction over d is a short in-register loop.
 #include "as_common.h"
+#include "column_stats.h"
 
 struct OutGeom {
   int kd, kh, kw, pad_d, pad_h, pad_w, dil, ntaps;
@@ -468,21 +469,16 @@ __global__ __launch_bounds__(256) void softargmax_fwd_kernel(const float* __rest
   if (i >= (long)B * HW) return;
   const long b = i / HW, pix = i % HW;
   const float* l = logits + b * D * HW + pix;
-  float m1 = -INFINITY, m2 = -INFINITY, sum = 0.f;
-  int am = 0;
-  for (int d = 0; d < D; ++d) {
-    const float v = l[d * HW];
-    sum += v;
-    if (v > m1) { m2 = m1; m1 = v; am = d; }
-    else if (v > m2) { m2 = v; }
-  }
+  ColTop2 st;
+  for (int d = 0; d < D; ++d) col_top2_step(st, l[d * HW], d);
+  const float m1 = st.m1;
   float se = 0.f;
   for (int d = 0; d < D; ++d) se += expf(l[d * HW] - m1);
   float acc = 0.f;
   for (int d = 0; d < D; ++d) acc += (expf(l[d * HW] - m1) / se) * (float)d;
   pred[i] = acc;
-  if (argmax) argmax[i] = am;
-  if (fcs) fcs[i] = (D > 2) ? m1 - (sum - m1 - m2) / (float)(D - 2) : 0.f;
+  if (argmax) argmax[i] = st.am;
+  if (fcs) fcs[i] = col_fcs(m1, st.m2, st.sum, D);
 }
 
 __global__ __launch_bounds__(256) void softargmax_bwd_kernel(const float* __restrict__ logits, const float* __restrict__ g_pred,

@@ -390,3 +390,25 @@ def test_command_line_visualize_writes_the_figures(nets, tmp_path):
   for p in written:
     with open(p, "rb") as f:
       assert f.read(5) == b"%PDF-"
+
+
+@pytest.mark.parametrize("D", [3, 5, 13, 25, 64])
+@pytest.mark.parametrize("lead", [(2, 3, 70), (1, 9, 67)], ids=["210px_idle_lanes", "603px_second_pixel"])
+def test_the_three_fcs_maps_are_one_map(lead, D):
+  """csrc/column_stats.h is the one definition of the FCS loop: as_softargmax_fwd's fcs, as_fcs_scores' mean map and the fcs
+  as_cost_volume_probe reports at its two picks are equal as int32 bit patterns, on a designed volume (ood_ref.make_volume:
+  the maximum twice, all equal, signed zeros) at 210 pixels (lanes of the 512-lane workgroup idle) and at 603 (some lanes take a
+  second pixel), for the first D of the 24- and 64-wide instances, the widest D and two narrow ones."""
+  B, H, W = lead
+  vol = ood_ref.make_volume((B, D, H, W), 20.0, nan=False)
+  assert not np.isnan(vol).any()
+  soft = softargmax_fcs(vol)
+  fm, _ = fcs_mean_map(vol)
+  assert np.array_equal(R.bits(soft), R.bits(fm)), "as_softargmax_fwd's fcs and as_fcs_scores' mean map differ"
+  pix, vals, _, _ = [t.cpu().numpy() for t in run(vol, profile=False)]
+  for b in range(B):
+    for which, arg in ((cv_probe.HI, np.argmax), (cv_probe.LO, np.argmin)):
+      row, col = int(pix[b, which, 0]), int(pix[b, which, 1])
+      assert row * W + col == int(arg(fm[b].ravel())), "the pick is not the extreme of the map"
+      f = vals[b, which, 0]
+      assert R.bits(f) == R.bits(fm[b, row, col]) == R.bits(soft[b, row, col]), (b, which, f, fm[b, row, col], soft[b, row, col])

@@ -4,6 +4,8 @@ on them: the reference's own maps (tests/golden/ood_fcs.npz), scipy's inverse no
 worked by hand."""
 import math
 import os
+import shutil
+import subprocess
 
 import numpy as np
 import pytest
@@ -73,6 +75,82 @@ def test_image_scores_are_the_fp64_mean_rounded_once():
   assert got[0, 0] == want0 and got[0, 1] == np.float32(2) * want0
   assert np.isnan(got[1]).all()
   assert R.ulp_gap(np.float32(1.0), np.nextafter(np.float32(1.0), np.float32(2.0))) == 1.0
+
+
+# ---- csrc/column_stats.h on the host ------------------------------------------------------------------------------------
+COLUMN_DS = (1, 2, 3, 4, 5, 12, 13, 24, 25, 64)
+
+
+def designed_columns(D):
+  """[n, D] fp32, one pattern per row: the maximum twice, all equal, ascending, descending, zeros of both signs (starting with
+  either), one -inf, values at gain 20 (the order of the fp32 sum shows), a NaN first, a NaN last."""
+  rs = np.random.RandomState(4242 + D)
+  f = np.float32
+  ramp = (np.arange(D, dtype=np.float32) - f(D // 2)) * f(0.7)
+  twice = rs.standard_normal(D).astype(np.float32)
+  twice[0] = twice[D - 1] = np.abs(twice).max() + f(1)
+  zeros = np.where(np.arange(D) % 2 == 0, f(0.0), f(-0.0)).astype(np.float32)
+  minf = rs.standard_normal(D).astype(np.float32)
+  minf[D // 2] = -np.inf
+  rows = [twice, np.full(D, 1.5, np.float32), ramp, ramp[::-1], zeros, -zeros, minf]
+  rows += [(rs.standard_normal(D) * 20.0).astype(np.float32) for _ in range(4)]
+  for at in (0, D - 1):
+    v = (rs.standard_normal(D) * 20.0).astype(np.float32)
+    v[at] = np.nan
+    rows.append(v)
+  return np.stack(rows)
+
+
+@pytest.fixture(scope="module")
+def column_stats_exe(tmp_path_factory):
+  if shutil.which("g++") is None:
+    pytest.skip("no g++")
+  exe = str(tmp_path_factory.mktemp("column_stats") / "column_stats_check")
+  src = os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools", "column_stats_check.cpp")
+  subprocess.run(["g++", "-O2", "-std=c++17", src, "-o", exe], check=True)
+  return exe
+
+
+@pytest.mark.parametrize("D", COLUMN_DS)
+def test_column_stats_header_is_the_restatement(column_stats_exe, tmp_path, D):
+  """col_top2_step and col_fcs of csrc/column_stats.h, compiled for the host, over designed columns: the fcs bits are
+  ood_ref.fcs_mean's (which is held to the reference's fixture above), am is numpy's first arg-max, m1 and m2 the two largest
+  values; a column with a NaN sets has_nan, for which ood_ref's rule (the map is NaN) is the callers' to apply."""
+  cols = designed_columns(D)
+  n = cols.shape[0]
+  path = str(tmp_path / "columns.txt")
+  with open(path, "w") as f:
+    f.write("%d %d\n" % (n, D))
+    for row in cols.view(np.uint32):
+      f.write(" ".join("%08x" % u for u in row) + "\n")
+  out = subprocess.run([column_stats_exe, path], capture_output=True, text=True, timeout=60)
+  assert out.returncode == 0, out.stdout + out.stderr
+  lines = out.stdout.split("\n")[:-1]
+  assert len(lines) == n
+  want = R.fcs_mean(np.ascontiguousarray(cols.T).reshape(1, D, 1, n))[0, 0]
+  for i, line in enumerate(lines):
+    fcs, m1, m2, am, has_nan = line.split()
+    col = cols[i]
+    assert int(has_nan) == int(np.isnan(col).any()), i
+    if int(has_nan):
+      assert np.isnan(want[i])
+      col = np.where(np.isnan(col), np.float32(-np.inf), col)        # a NaN compares false: it never becomes the maximum
+    else:
+      assert int(fcs, 16) == int(want[i:i + 1].view(np.uint32)[0]), (i, fcs, want[i])
+    top = np.sort(np.concatenate([col, np.full(1, -np.inf, np.float32)]))[::-1]
+    assert int(am) == int(np.argmax(col)), i
+    got = np.array([int(m1, 16), int(m2, 16)], np.uint32).view(np.float32)
+    assert got[0] == top[0] and got[1] == top[1], (i, got, top[:2])
+  if D >= 2:
+    assert lines[0].split()[1] == lines[0].split()[2] and lines[0].split()[3] == "0"      # the maximum twice: m2 == m1, first index
+
+
+def test_row_cursor_refuses_before_any_device_call():
+  from adaptive_stereo import collect
+  with pytest.raises(ValueError, match="capacity 0 must be at least 1"):
+    collect.RowCursor("X", 0, "cuda")
+  with pytest.raises(RuntimeError, match="no CPU path"):
+    collect.RowCursor("X", 1, "cpu")
 
 
 # ---- threshold ----------------------------------------------------------------------------------------------------------

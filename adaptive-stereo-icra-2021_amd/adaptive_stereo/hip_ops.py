@@ -734,21 +734,19 @@ def block_forward_act(z_prev, a_prevprev, st_prev: BnState, g: Pcl, shape: ConvS
   dev = z_prev.device
   lib = nat.load()
   a_prev, z = POOL.get(g, dev), POOL.get(g, dev)
+  # the route: entry point, the weights packed for it, BatchNorm partials of a launch
   if _WINOGRAD and lib.as_conv32_wino_ok(g, g, shape) == 1:
     # F(2x2, 3x3): 4 matrix products per output pixel instead of 9; the transformed filters come out of the step's one
     # packing launch like every other weight-derived buffer
     ww = pack_special(w, PACK_WINO, 16, 16 * 1024,
                       lambda w_, o_: call("as_conv32_wino_pack_weights", ptr(w_), ptr(o_), 0, stream()))
-    stats = StatParts(lib.as_conv32_wino_parts(), dev)
-    call("as_conv32_wino_fwd", ptr(z_prev), ptr(a_prevprev), ptr(st_prev.scale), ptr(st_prev.shift), ptr(a_prev), g, ptr(ww),
-         ptr(b), LEAKY_SLOPE, ptr(z), g, shape, ptr(stats.mean), ptr(stats.m2), ptr(stats.cnt), stream())
-    return a_prev, z, bn_train_stats(stats, gamma, beta, rm, rv)
-  wp = pack_weights(w, shape, False)
-  stats = StatParts(lib.as_conv32_act_parts(), dev)
-  call("as_conv32_act_fwd", ptr(z_prev), ptr(a_prevprev), ptr(st_prev.scale), ptr(st_prev.shift), ptr(a_prev), g, ptr(wp), ptr(b),
+    entry, wp, parts = "as_conv32_wino_fwd", ww, lib.as_conv32_wino_parts()
+  else:
+    entry, wp, parts = "as_conv32_act_fwd", pack_weights(w, shape, False), lib.as_conv32_act_parts()
+  stats = StatParts(parts, dev)
+  call(entry, ptr(z_prev), ptr(a_prevprev), ptr(st_prev.scale), ptr(st_prev.shift), ptr(a_prev), g, ptr(wp), ptr(b),
        LEAKY_SLOPE, ptr(z), g, shape, ptr(stats.mean), ptr(stats.m2), ptr(stats.cnt), stream())
-  st = bn_train_stats(stats, gamma, beta, rm, rv)
-  return a_prev, z, st
+  return a_prev, z, bn_train_stats(stats, gamma, beta, rm, rv)
 
 
 def block_backward(g_out, x, z, st, w, gamma, g: Pcl, shape: ConvShape, train, skip, need_dx, sinks=None,
@@ -774,26 +772,24 @@ def block_backward(g_out, x, z, st, w, gamma, g: Pcl, shape: ConvShape, train, s
     g_x = POOL.get(g, dev)
     nws = _empty(lib.as_bn_bwd_workspace(g), dev)
     next_z, next_st = next_bn
+    # the route: entry point, the data gradient's filter packed for it, its workspace and parts queries
     if _WINOGRAD and _WINOGRAD_BWD and lib.as_conv32_wino_ok(g, g, shape) == 1:
       # both gradients by minimal filtering, 4 matrix products per pixel and gradient instead of 9, in one launch
       # (csrc/conv32_wino_bwd.hip): g_z stays in LDS between the data-gradient and the weight-gradient waves
       ww_t = pack_special(w, PACK_WINO_T, 16, 16 * 1024,
                           lambda w_, o_: call("as_conv32_wino_pack_weights", ptr(w_), ptr(o_), 1, stream()))
-      wws = _empty(lib.as_conv32_wino_bwd_fused_workspace(), dev)
-      _keep_for_deferred_reduce(wws)
-      with _rmw(sw):
-        call("as_conv32_wino_bwd_fused", ptr(x), g, ptr(g_out), ptr(z), g, shape, ptr(ww_t), ptr(st.scale), ptr(st.shift),
-             ptr(st.mean), ptr(coef), LEAKY_SLOPE, ptr(next_z), ptr(next_st.scale), ptr(next_st.shift), ptr(next_st.mean),
-             ptr(g_x), ptr(sw), ptr(sb), 1, ptr(nws), ptr(wws), stream())
-      return g_x, None, None, None, None, BnBwdSums(nws, lib.as_conv32_wino_bwd_fused_parts())
-    wp_t = pack_weights(w, shape, True)
-    wws = _empty(lib.as_conv32_bwd_fused_workspace(), dev)
+      entry, wp_t = "as_conv32_wino_bwd_fused", ww_t
+      workspace, parts = lib.as_conv32_wino_bwd_fused_workspace, lib.as_conv32_wino_bwd_fused_parts
+    else:
+      entry, wp_t = "as_conv32_bwd_fused", pack_weights(w, shape, True)
+      workspace, parts = lib.as_conv32_bwd_fused_workspace, lib.as_conv32_bwd_fused_parts
+    wws = _empty(workspace(), dev)
     _keep_for_deferred_reduce(wws)
     with _rmw(sw):
-      call("as_conv32_bwd_fused", ptr(x), g, ptr(g_out), ptr(z), g, shape, ptr(wp_t), ptr(st.scale), ptr(st.shift), ptr(st.mean),
-           ptr(coef), LEAKY_SLOPE, ptr(next_z), ptr(next_st.scale), ptr(next_st.shift), ptr(next_st.mean), ptr(g_x), ptr(sw),
-           ptr(sb), 1, ptr(nws), ptr(wws), stream())
-    return g_x, None, None, None, None, BnBwdSums(nws, lib.as_conv32_bwd_fused_parts())
+      call(entry, ptr(x), g, ptr(g_out), ptr(z), g, shape, ptr(wp_t), ptr(st.scale), ptr(st.shift), ptr(st.mean), ptr(coef),
+           LEAKY_SLOPE, ptr(next_z), ptr(next_st.scale), ptr(next_st.shift), ptr(next_st.mean), ptr(g_x), ptr(sw), ptr(sb), 1,
+           ptr(nws), ptr(wws), stream())
+    return g_x, None, None, None, None, BnBwdSums(nws, parts())
   if all_sunk and \
       lib.as_conv32_wgrad_bnapply_ok(g, g, shape) == 1:
     # stages 1-2 of the BatchNorm backward only (stage 1 may already be in `sums`); stage 3 rides on the weight gradient,

@@ -418,14 +418,10 @@ int agg3d_units(const as_pcl* g) {
 template <int IN, int EPI, bool STRIP>
 static int agg_launch_s(const Agg3dArgs& a, int lds_bytes, hipStream_t st) {
   static AsPerDevice attr_set;
-  if (!attr_set.get()) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(agg3d_kernel<IN, EPI, STRIP>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) { as_set_error("as_agg3d_fwd: %s", hipGetErrorString(e)); return AS_ERR_LAUNCH; }
-    attr_set.set();
-  }
-  hipLaunchKernelGGL((agg3d_kernel<IN, EPI, STRIP>), dim3(8 * a.per_xcd), dim3(256), lds_bytes, st, a);
-  return AS_OK;
+  Agg3dArgs args = a;
+  void* kargs[] = {&args};
+  return as_launch_lds(reinterpret_cast<const void*>(agg3d_kernel<IN, EPI, STRIP>), attr_set, 160 * 1024, lds_bytes,
+                       dim3(8 * a.per_xcd), dim3(256), kargs, "as_agg3d_fwd", st);
 }
 template <int IN, int EPI>
 static int agg_launch_t(const Agg3dArgs& a, int lds_bytes, hipStream_t st) {

@@ -393,14 +393,10 @@ extern "C" int as_agg_tail_ok(const as_pcl* g) {
 template <int IN, int NK, bool OUT>
 static int tail_launch_t(const TailArgs& a, int grid, int lds_bytes, hipStream_t st) {
   static AsPerDevice attr_set;
-  if (!attr_set.get()) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(agg_tail_kernel<IN, NK, OUT>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) { as_set_error("as_agg_tail_fwd: %s", hipGetErrorString(e)); return AS_ERR_LAUNCH; }
-    attr_set.set();
-  }
-  hipLaunchKernelGGL((agg_tail_kernel<IN, NK, OUT>), dim3(grid), dim3(256), lds_bytes, st, a);
-  return AS_OK;
+  TailArgs args = a;
+  void* kargs[] = {&args};
+  return as_launch_lds(reinterpret_cast<const void*>(agg_tail_kernel<IN, NK, OUT>), attr_set, 160 * 1024, lds_bytes, dim3(grid),
+                       dim3(256), kargs, "as_agg_tail_fwd", st);
 }
 // positions per workgroup of the direct kernel: 16 while 32 would give fewer than two workgroups per CU (4 pairs at 24 x 78:
 // 240 of 32).  npos = positions of the flattened padded plane, (H - 1) Wp + W.  The launcher and as_agg_tail_fwd_positions.

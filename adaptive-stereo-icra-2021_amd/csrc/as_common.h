@@ -91,6 +91,24 @@ struct AsPerDevice {
   void set() { const int d = dev(); if (d >= 0) done[d] = true; }
 };
 
+// The one launch of a kernel with dynamic LDS: raises the kernel's MaxDynamicSharedMemorySize to attr_bytes once per device
+// (`once` belongs to this kernel instantiation), launches with lds_bytes <= attr_bytes, and reports either failure under
+// `who`, the entry point that was actually called.  kargs: hipLaunchKernel's array of pointers to the kernel arguments.
+static inline int as_launch_lds(const void* fn, AsPerDevice& once, int attr_bytes, int lds_bytes, dim3 grid, dim3 block,
+                                void** kargs, const char* who, hipStream_t st) {
+  if (!once.get()) {
+    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, attr_bytes);
+    if (e != hipSuccess) {
+      as_set_error("%s: cannot reserve %d bytes of LDS: %s", who, attr_bytes, hipGetErrorString(e));
+      return AS_ERR_LAUNCH;
+    }
+    once.set();
+  }
+  hipError_t le = hipLaunchKernel(fn, grid, block, kargs, lds_bytes, st);
+  if (le != hipSuccess) { as_set_error("%s: launch failed: %s", who, hipGetErrorString(le)); return AS_ERR_LAUNCH; }
+  return AS_OK;
+}
+
 static inline int as_div_up(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
 // Wave-level sum over all 64 lanes (result in every lane).

@@ -23,7 +23,7 @@
 // Measured at 4 pairs: 328-336 us per layer (65-67 % of the fp32 matrix peak) against 411-425 us for the two launches.
 #include "as_common.h"
 #include "conv_epilogue.h"
-#include "conv32_act.h"
+#include "conv32_layer.h"
 
 #define CA_W 144                        // staged voxels per row: 8 + 128 + 8
 #define CA_ROW_BYTES (CA_W * 128)       // 18,432
@@ -319,25 +319,16 @@ bool conv32_act_applicable(const as_pcl* gin, const as_pcl* gout, const as_conv_
 
 int conv32_act_parts(void) { return ca_grid(); }
 
-int conv32_act_launch(const float* z_prev, const float* a_prevprev, const float* in_scale, const float* in_shift, float* a_out,
-                      const as_pcl* g, const as_conv_shape* s, const float* packed_w, const float* bias, float slope,
-                      float* z, float* stat_mean, float* stat_m2, float* stat_cnt, void* stream) {
+int conv32_act_launch(const LayerFwdArgs& f, const as_pcl* g, const as_conv_shape* s, const char* who, void* stream) {
   static AsPerDevice attr_set[2];
-  const int fi = a_prevprev != nullptr ? 1 : 0;
+  const int fi = f.a_prevprev != nullptr ? 1 : 0;
   const void* fn = fi ? reinterpret_cast<const void*>(conv32_act_kernel<true>) : reinterpret_cast<const void*>(conv32_act_kernel<false>);
-  if (!attr_set[fi].get()) {
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, CA_LDS_BYTES);
-    if (e != hipSuccess) { as_set_error("as_conv32_act_fwd: %s", hipGetErrorString(e)); return AS_ERR_LAUNCH; }
-    attr_set[fi].set();
-  }
   ActArgs a;
-  a.zin = z_prev; a.ain = a_prevprev; a.in_scale = in_scale; a.in_shift = in_shift; a.a_out = a_out; a.wq = packed_w;
-  a.ep.bias = bias; a.ep.z = z; a.ep.ep_scale = nullptr; a.ep.ep_shift = nullptr; a.ep.residual = nullptr;
-  a.ep.stat_mean = stat_mean; a.ep.stat_m2 = stat_m2; a.ep.stat_cnt = stat_cnt; a.ep.epilogue = 0; a.ep.slope = slope;
+  a.zin = f.z_prev; a.ain = f.a_prevprev; a.in_scale = f.in_scale; a.in_shift = f.in_shift; a.a_out = f.a_out; a.wq = f.w;
+  a.ep.bias = f.bias; a.ep.z = f.z; a.ep.ep_scale = nullptr; a.ep.ep_shift = nullptr; a.ep.residual = nullptr;
+  a.ep.stat_mean = f.stat_mean; a.ep.stat_m2 = f.stat_m2; a.ep.stat_cnt = f.stat_cnt; a.ep.epilogue = 0; a.ep.slope = f.slope;
   a.g = as_make_dev(g);
-  a.dil = s->dil; a.nseg = (g->W + 127) / 128; a.slope = slope;
+  a.dil = s->dil; a.nseg = (g->W + 127) / 128; a.slope = f.slope;
   void* kargs[] = {&a};
-  hipError_t le = hipLaunchKernel(fn, dim3(ca_grid()), dim3(256), kargs, CA_LDS_BYTES, (hipStream_t)stream);
-  if (le != hipSuccess) { as_set_error("as_conv32_act_fwd: launch failed: %s", hipGetErrorString(le)); return AS_ERR_LAUNCH; }
-  return AS_OK;
+  return as_launch_lds(fn, attr_set[fi], CA_LDS_BYTES, CA_LDS_BYTES, dim3(ca_grid()), dim3(256), kargs, who, (hipStream_t)stream);
 }

@@ -30,9 +30,7 @@
 // Measured at 4 pairs: 605-630 us per layer = 70-72 % of the fp32 matrix peak for both gradients (DESIGN 4 has the phase
 // costs and what the first versions lost where).
 #include "as_common.h"
-#include "conv32_bwd.h"
-#include <cstdio>
-#include <cstdlib>
+#include "conv32_layer.h"
 
 #define BW_W 80                         // staged voxels per row: 8 + 64 + 8
 #define BW_PITCH 144                    // bytes per staged g_z voxel (128 + 16: consecutive voxels 4 banks apart)
@@ -446,37 +444,25 @@ bool conv32_bwd_fused_applicable(const as_pcl* gin, const as_pcl* gout, const as
 
 int conv32_bwd_fused_slabs(void) { return bw_grid(); }
 
-int conv32_bwd_fused_launch(const float* x, const float* g_a, const float* z, const as_pcl* g, const as_conv_shape* s,
-                            const float* packed_wt, const float* scale, const float* shift, const float* mean,
-                            const float* coef, float slope, const float* next_z, const float* next_scale,
-                            const float* next_shift, const float* next_mean, float* g_x, float* partial,
-                            float* partial_db, double* next_partial, void* stream) {
+int conv32_bwd_fused_launch(const LayerBwdArgs& b, const as_pcl* g, const as_conv_shape* s, const char* who, void* stream) {
   static AsPerDevice attr_set;
-  if (!attr_set.get()) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv32_bwd_fused_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, BW_LDS_BYTES);
-    if (e != hipSuccess) { as_set_error("as_conv32_bwd_fused: %s", hipGetErrorString(e)); return AS_ERR_LAUNCH; }
-    attr_set.set();
-  }
   BwdArgs a;
-  a.x = x; a.ga = g_a; a.z = z; a.wq = packed_wt; a.bn_scale = scale; a.bn_shift = shift; a.bn_mean = mean; a.bn_coef = coef;
-  a.nz = next_z; a.n_scale = next_scale; a.n_shift = next_shift; a.n_mean = next_mean;
-  a.gx = g_x; a.partial = partial; a.partial_db = partial_db; a.n_partial = next_partial;
+  a.x = b.x; a.ga = b.g_a; a.z = b.z; a.wq = b.w; a.bn_scale = b.scale; a.bn_shift = b.shift; a.bn_mean = b.mean; a.bn_coef = b.coef;
+  a.nz = b.next_z; a.n_scale = b.next_scale; a.n_shift = b.next_shift; a.n_mean = b.next_mean;
+  a.gx = b.g_x; a.partial = b.partial; a.partial_db = b.partial_db; a.n_partial = b.next_partial;
   a.g = as_make_dev(g);
-  a.dil = s->dil; a.slope = slope;
+  a.dil = s->dil; a.slope = b.slope;
   a.nseg = (g->W + 63) / 64;
 #ifdef BW_TIMING_BUILD
   static long long* timing_buf = nullptr;
   const size_t timing_bytes = (size_t)BW_GRID * 4 * 8 * 8;
-  if (!timing_buf) hipMalloc(&timing_buf, timing_bytes);
-  hipMemsetAsync(timing_buf, 0, timing_bytes, (hipStream_t)stream);
-  a.timing = timing_buf;
+  a.timing = as_timing_begin(timing_buf, timing_bytes, (hipStream_t)stream);
 #endif
-  hipLaunchKernelGGL(conv32_bwd_fused_kernel, dim3(bw_grid()), dim3(256), BW_LDS_BYTES, (hipStream_t)stream, a);
+  void* kargs[] = {&a};
+  if (int e = as_launch_lds(reinterpret_cast<const void*>(conv32_bwd_fused_kernel), attr_set, BW_LDS_BYTES, BW_LDS_BYTES,
+                            dim3(bw_grid()), dim3(256), kargs, who, (hipStream_t)stream)) return e;
 #ifdef BW_TIMING_BUILD
-  if (getenv("AS_BW_TIMING")) {                            // dump THIS launch (synchronises: diagnostic build only)
-    hipStreamSynchronize((hipStream_t)stream);
-    void* hbuf = malloc(timing_bytes); hipMemcpy(hbuf, timing_buf, timing_bytes, hipMemcpyDeviceToHost);
+  if (void* hbuf = as_timing_fetch("AS_BW_TIMING", timing_buf, timing_bytes, (hipStream_t)stream)) {   // dump THIS launch
     FILE* f = fopen("gpurun_out/bwd_timing.bin", "wb"); if (f) { fwrite(hbuf, 1, timing_bytes, f); fclose(f); } free(hbuf);
   }
 #endif

@@ -416,14 +416,6 @@ int conv32_lds_launch(const float* x, const as_pcl* gin, const float* packed_w, 
 #undef AS_LDS_PICK
   static AsPerDevice attr_set[9];
   const int fi = res_self ? 8 : mode * 2 + (has_res ? 1 : 0);
-  if (!attr_set[fi].get()) {
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, TL_LDS_BYTES);
-    if (e != hipSuccess) {
-      as_set_error("conv32_lds: cannot reserve %d bytes of LDS: %s", TL_LDS_BYTES, hipGetErrorString(e));
-      return AS_ERR_LAUNCH;
-    }
-    attr_set[fi].set();
-  }
 #ifdef AS_LDS_TRACE_BUILD
   static int trace_countdown = -2;
   static unsigned long long* trace_buf = nullptr;
@@ -437,8 +429,7 @@ int conv32_lds_launch(const float* x, const as_pcl* gin, const float* packed_w, 
   const int prof_id = mode == 3 ? 6 : 2;
   as_prof_mark(prof_id, st, 1, 0.0);
   void* kargs[] = {&a};
-  hipError_t le = hipLaunchKernel(fn, dim3(grid), dim3(256), kargs, TL_LDS_BYTES, st);
-  if (le != hipSuccess) { as_set_error("as_conv32_fwd(lds): launch failed: %s", hipGetErrorString(le)); return AS_ERR_LAUNCH; }
+  if (int e = as_launch_lds(fn, attr_set[fi], TL_LDS_BYTES, TL_LDS_BYTES, dim3(grid), dim3(256), kargs, "as_conv32_fwd(lds)", st)) return e;
 #ifdef AS_LDS_TRACE_BUILD
   if (a.trace) {
     hipStreamSynchronize(st);
@@ -768,22 +759,7 @@ bool conv32_wgrad_bnapply_ok(const as_pcl* gout) { return wgrad_lds2(gout); }
 int conv32_wgrad_lds_launch(const float* x, const as_pcl* gin, const float* gz, const as_pcl* gout,
                             const as_conv_shape* s, float* partial, float* partial_db, const WgradBnApply* bn,
                             void* stream) {
-  static AsPerDevice attr_set;
-  if (!attr_set.get()) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv32_wgrad_lds_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, TLW_LDS_BYTES);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv32_wgrad_lds2_kernel<false>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, TLW2_LDS_BYTES);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv32_wgrad_lds2_kernel<true>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, TLW2A_LDS_BYTES);
-    if (e != hipSuccess) {
-      as_set_error("conv32_wgrad_lds: cannot reserve %d bytes of LDS: %s", TLW2_LDS_BYTES, hipGetErrorString(e));
-      return AS_ERR_LAUNCH;
-    }
-    attr_set.set();
-  }
+  static AsPerDevice attr_set[3];                          // per kernel, each at its first launch
   WgradLdsArgs a;
   a.x = x; a.gz = gz; a.partial = partial; a.partial_db = partial_db;
   a.gin = as_make_dev(gin); a.gout = as_make_dev(gout);
@@ -798,11 +774,14 @@ int conv32_wgrad_lds_launch(const float* x, const as_pcl* gin, const float* gz, 
     if (!wgrad_lds2(gout)) { as_set_error("as_conv32_wgrad_bnapply: configuration not supported"); return AS_ERR_ARG; }
     a.bn_z = bn->z; a.bn_scale = bn->scale; a.bn_shift = bn->shift; a.bn_mean = bn->mean; a.bn_coef = bn->coef;
     a.gz_out = bn->gz_out; a.slope = bn->slope;
-    hipLaunchKernelGGL(conv32_wgrad_lds2_kernel<true>, dim3(grid), dim3(512), TLW2A_LDS_BYTES, (hipStream_t)stream, a);
-  } else if (wgrad_lds2(gout))
-    hipLaunchKernelGGL(conv32_wgrad_lds2_kernel<false>, dim3(grid), dim3(512), TLW2_LDS_BYTES, (hipStream_t)stream, a);
-  else
-    hipLaunchKernelGGL(conv32_wgrad_lds_kernel, dim3(grid), dim3(256), TLW_LDS_BYTES, (hipStream_t)stream, a);
-  AS_CHECK_LAUNCH("as_conv32_wgrad(lds)");
-  return AS_OK;
+  }
+  // 0: one workgroup-row form, 1: wgrad_lds2's 512-thread form, 2: the same with stage 3 of the BatchNorm backward on the way in
+  const int ki = bn != nullptr ? 2 : (wgrad_lds2(gout) ? 1 : 0);
+  const void* const fn[3] = {reinterpret_cast<const void*>(conv32_wgrad_lds_kernel),
+                             reinterpret_cast<const void*>(conv32_wgrad_lds2_kernel<false>),
+                             reinterpret_cast<const void*>(conv32_wgrad_lds2_kernel<true>)};
+  const int lds[3] = {TLW_LDS_BYTES, TLW2_LDS_BYTES, TLW2A_LDS_BYTES};
+  void* kargs[] = {&a};
+  return as_launch_lds(fn[ki], attr_set[ki], lds[ki], lds[ki], dim3(grid), dim3(ki ? 512 : 256), kargs, "as_conv32_wgrad(lds)",
+                       (hipStream_t)stream);
 }

@@ -29,9 +29,7 @@
 #include "conv32_lds.h"
 #include <cstdlib>
 #include "conv3d_lds.h"
-#include "conv32_bwd.h"
-#include "conv32_act.h"
-#include "conv32_wino.h"
+#include "conv32_layer.h"
 #include "conv32_s2.h"
 
 static bool wgrad_lds_applicable(const as_pcl* gin, const as_pcl* gout, const as_conv_shape* s);
@@ -581,7 +579,7 @@ static int fill_taps(const as_pcl* gin, const as_conv_shape* s, int* tap_off, co
   return AS_OK;
 }
 
-static int check_conv(const as_pcl* gin, const as_pcl* gout, const as_conv_shape* s, const char* who) {
+int check_conv(const as_pcl* gin, const as_pcl* gout, const as_conv_shape* s, const char* who) {
   AS_CHECK_ARG(as_pcl_ok(gin) && as_pcl_ok(gout) && s, "%s: bad geometry", who);
   AS_CHECK_ARG(gin->B == gout->B && gin->D == gout->D, "%s: batch/depth mismatch", who);
   // output extent of the convolution
@@ -858,231 +856,6 @@ extern "C" int as_conv32_wgrad_bnapply(const float* x, const as_pcl* gin, const 
   as_prof_mark(3, st, 0, 2.0 * (double)gout->B * gout->D * gout->H * gout->W * 1024.0 * T);
   wgrad_reduce(st, workspace, partial_db, slabs, T, dW, db, accumulate);
   AS_CHECK_LAUNCH("as_conv32_wgrad_bnapply(reduce)");
-  return AS_OK;
-}
-
-// Whole backward of a full-resolution layer in one launch (conv32_bwd.hip): stage 3 of its BatchNorm backward, data gradient
-// + skip connection, weight / bias gradient, stage 1 of the next BatchNorm backward.
-extern "C" int as_conv32_bwd_fused_ok(const as_pcl* gin, const as_pcl* gout, const as_conv_shape* s) {
-  if (!as_pcl_ok(gin) || !as_pcl_ok(gout) || !s) return AS_ERR_ARG;
-  return conv32_bwd_fused_applicable(gin, gout, s) ? 1 : 0;
-}
-extern "C" int as_conv32_bwd_fused_parts(void) { return conv32_bwd_fused_slabs(); }
-extern "C" int64_t as_conv32_bwd_fused_workspace(void) { return (int64_t)conv32_bwd_fused_slabs() * (9 * 1024 + 32); }
-
-extern "C" int as_conv32_bwd_fused(const float* x, const as_pcl* gin, const float* g_a, const float* z, const as_pcl* gout,
-                                   const as_conv_shape* s, const float* packed_wt, const float* scale, const float* shift,
-                                   const float* mean, const float* coef, float slope, const float* next_z,
-                                   const float* next_scale, const float* next_shift, const float* next_mean, float* g_x,
-                                   float* dW, float* db, int accumulate, float* next_bn_workspace, float* workspace,
-                                   void* stream) {
-  if (int e = check_conv(gin, gout, s, "as_conv32_bwd_fused")) return e;
-  AS_CHECK_ARG(x && g_a && z && packed_wt && scale && shift && mean && coef && next_z && next_scale && next_shift && next_mean &&
-               g_x && dW && next_bn_workspace && workspace, "as_conv32_bwd_fused: null pointer");
-  AS_CHECK_ARG(conv32_bwd_fused_applicable(gin, gout, s), "as_conv32_bwd_fused: configuration not supported (as_conv32_bwd_fused_ok() == 0)");
-  AS_CHECK_ARG(((uintptr_t)next_bn_workspace & 7) == 0, "as_conv32_bwd_fused: the BatchNorm workspace must be 8-byte aligned");
-  AS_CHECK_ARG(g_x != g_a && g_x != x && g_x != z, "as_conv32_bwd_fused: g_x must not alias an input");
-  const int T = 9;
-  const int slabs = conv32_bwd_fused_slabs();
-  float* partial_db = workspace + (int64_t)slabs * T * 1024;
-  hipStream_t st = (hipStream_t)stream;
-  as_prof_mark(AS_PROF_BWD_FUSED, st, 1, 0.0);
-  if (int e = conv32_bwd_fused_launch(x, g_a, z, gout, s, packed_wt, scale, shift, mean, coef, slope, next_z, next_scale,
-                                      next_shift, next_mean, g_x, workspace, partial_db,
-                                      reinterpret_cast<double*>(next_bn_workspace), stream)) return e;
-  as_prof_mark(AS_PROF_BWD_FUSED, st, 0, 2.0 * 2.0 * (double)gout->B * gout->H * gout->W * 1024.0 * T);   // dgrad + wgrad
-  AS_CHECK_LAUNCH("as_conv32_bwd_fused");
-  wgrad_reduce(st, workspace, partial_db, slabs, T, dW, db, accumulate);
-  AS_CHECK_LAUNCH("as_conv32_bwd_fused(reduce)");
-  return AS_OK;
-}
-
-// Training forward of a full-resolution layer whose operand is the PREVIOUS layer's output, formed on the way in from that
-// layer's pre-activation, BatchNorm affine and skip input (csrc/conv32_act.hip).
-extern "C" int as_conv32_act_ok(const as_pcl* gin, const as_pcl* gout, const as_conv_shape* s) {
-  if (!as_pcl_ok(gin) || !as_pcl_ok(gout) || !s) return AS_ERR_ARG;
-  return conv32_act_applicable(gin, gout, s) ? 1 : 0;
-}
-extern "C" int as_conv32_act_parts(void) { return conv32_act_parts(); }
-
-extern "C" int as_conv32_act_fwd(const float* z_prev, const float* a_prevprev, const float* in_scale, const float* in_shift,
-                                 float* a_out, const as_pcl* gin, const float* packed_w, const float* bias, float slope,
-                                 float* z, const as_pcl* gout, const as_conv_shape* s, float* stat_mean, float* stat_m2,
-                                 float* stat_cnt, void* stream) {
-  if (int e = check_conv(gin, gout, s, "as_conv32_act_fwd")) return e;
-  AS_CHECK_ARG(z_prev && in_scale && in_shift && a_out && packed_w && z, "as_conv32_act_fwd: null pointer");
-  AS_CHECK_ARG((stat_mean != nullptr) == (stat_m2 != nullptr) && (stat_mean != nullptr) == (stat_cnt != nullptr),
-               "as_conv32_act_fwd: pass all three moment arrays or none");
-  AS_CHECK_ARG(conv32_act_applicable(gin, gout, s), "as_conv32_act_fwd: configuration not supported (as_conv32_act_ok() == 0)");
-  AS_CHECK_ARG(slope > 0.f && slope < 1.f, "as_conv32_act_fwd: slope must lie in (0, 1)");
-  AS_CHECK_ARG(a_out != z_prev && a_out != a_prevprev && z != z_prev && z != a_out && z != a_prevprev,
-               "as_conv32_act_fwd: outputs must not alias inputs or each other");
-  hipStream_t st = (hipStream_t)stream;
-  as_prof_mark(AS_PROF_CONV_ACT, st, 1, 0.0);
-  if (int e = conv32_act_launch(z_prev, a_prevprev, in_scale, in_shift, a_out, gout, s, packed_w, bias, slope, z, stat_mean,
-                                stat_m2, stat_cnt, stream)) return e;
-  as_prof_mark(AS_PROF_CONV_ACT, st, 0, 2.0 * (double)gout->B * gout->H * gout->W * 1024.0 * 9);
-  AS_CHECK_LAUNCH("as_conv32_act_fwd");
-  return AS_OK;
-}
-
-// The same layer by the minimal-filtering algorithm F(2x2, 3x3) (csrc/conv32_wino.hip): 4 matrix products per output pixel
-// instead of 9.  wino_w: as_conv32_wino_pack_weights (or a batch job of kind AS_PACK_WINO).
-extern "C" int as_conv32_wino_ok(const as_pcl* gin, const as_pcl* gout, const as_conv_shape* s) {
-  if (!as_pcl_ok(gin) || !as_pcl_ok(gout) || !s) return AS_ERR_ARG;
-  return conv32_wino_applicable(gin, gout, s) ? 1 : 0;
-}
-extern "C" int as_conv32_wino_parts(void) { return conv32_wino_parts(); }
-
-extern "C" int as_conv32_wino_fwd(const float* z_prev, const float* a_prevprev, const float* in_scale, const float* in_shift,
-                                  float* a_out, const as_pcl* gin, const float* wino_w, const float* bias, float slope,
-                                  float* z, const as_pcl* gout, const as_conv_shape* s, float* stat_mean, float* stat_m2,
-                                  float* stat_cnt, void* stream) {
-  if (int e = check_conv(gin, gout, s, "as_conv32_wino_fwd")) return e;
-  AS_CHECK_ARG(z_prev && in_scale && in_shift && a_out && wino_w && z, "as_conv32_wino_fwd: null pointer");
-  AS_CHECK_ARG((stat_mean != nullptr) == (stat_m2 != nullptr) && (stat_mean != nullptr) == (stat_cnt != nullptr),
-               "as_conv32_wino_fwd: pass all three moment arrays or none");
-  AS_CHECK_ARG(conv32_wino_applicable(gin, gout, s), "as_conv32_wino_fwd: configuration not supported (as_conv32_wino_ok() == 0)");
-  AS_CHECK_ARG(slope > 0.f && slope < 1.f, "as_conv32_wino_fwd: slope must lie in (0, 1)");
-  AS_CHECK_ARG(a_out != z_prev && a_out != a_prevprev && z != z_prev && z != a_out && z != a_prevprev,
-               "as_conv32_wino_fwd: outputs must not alias inputs or each other");
-  hipStream_t st = (hipStream_t)stream;
-  as_prof_mark(AS_PROF_WINO_FWD, st, 1, 0.0);
-  if (int e = conv32_wino_launch(z_prev, a_prevprev, in_scale, in_shift, a_out, gout, s, wino_w, bias, slope, z, stat_mean,
-                                 stat_m2, stat_cnt, stream)) return e;
-  // (ALGORITHMIC flops: the direct form's 9 taps — what the layer computes, not the 4 products per pixel it executes)
-  as_prof_mark(AS_PROF_WINO_FWD, st, 0, 2.0 * (double)gout->B * gout->H * gout->W * 1024.0 * 9);
-  AS_CHECK_LAUNCH("as_conv32_wino_fwd");
-  return AS_OK;
-}
-
-// Eval-mode BasicBlock by minimal filtering: out = lrelu((conv(x) + bias) * scale + shift) (+ x).  One read of x (the skip
-// connection comes out of the staged rows), one write.
-extern "C" int as_conv32_wino_eval(const float* x, const as_pcl* g, const as_conv_shape* s, const float* wino_w, const float* bias,
-                                   const float* scale, const float* shift, float slope, int residual, float* out, void* stream) {
-  if (int e = check_conv(g, g, s, "as_conv32_wino_eval")) return e;
-  AS_CHECK_ARG(x && wino_w && scale && shift && out, "as_conv32_wino_eval: null pointer");
-  AS_CHECK_ARG(conv32_wino_applicable(g, g, s), "as_conv32_wino_eval: configuration not supported (as_conv32_wino_ok() == 0)");
-  AS_CHECK_ARG(slope > 0.f && slope < 1.f, "as_conv32_wino_eval: slope must lie in (0, 1)");
-  AS_CHECK_ARG(out != x, "as_conv32_wino_eval: out must not alias x");
-  hipStream_t st = (hipStream_t)stream;
-  as_prof_mark(AS_PROF_WINO_FWD, st, 1, 0.0);
-  if (int e = conv32_wino_eval_launch(x, g, s, wino_w, bias, scale, shift, slope, residual, out, stream)) return e;
-  as_prof_mark(AS_PROF_WINO_FWD, st, 0, 2.0 * (double)g->B * g->H * g->W * 1024.0 * 9);
-  AS_CHECK_LAUNCH("as_conv32_wino_eval");
-  return AS_OK;
-}
-
-// Backward of the same layer by minimal filtering, two launches: data gradient F(2x2, 3x3) with stage 3 of the BatchNorm
-// backward on the way in (g_z written once), skip connection and next-BatchNorm sums in the epilogue; then weight / bias
-// gradient F(3x3, 2x2) from x and g_z.  Arguments as as_conv32_bwd_fused, plus g_z (a PCL buffer of the layer's geometry).
-extern "C" int as_conv32_wino_bwd_parts(void) { return conv32_wino_dgrad_parts(); }
-// Which data-gradient kernel as_conv32_wino_bwd_data launches: 2 (default) = conv32_wino_dgrad.hip where it is the faster one
-// (dilation 1, 2, 4), 1 = conv32_wino.hip MODE 2 everywhere, 3 = conv32_wino_dgrad.hip everywhere (its dilation-8 instantiation
-// is slower than generation 1 and only here for the parity tests).  All write the same bits; returns the previous setting.
-static int g_wino_dgrad_generation = 2;
-extern "C" int as_conv32_wino_bwd_generation(int generation) {
-  const int prev = g_wino_dgrad_generation;
-  if (generation >= 1 && generation <= 3) g_wino_dgrad_generation = generation;
-  return prev;
-}
-extern "C" int64_t as_conv32_wino_bwd_workspace(void) { return (int64_t)conv32_wino_wgrad_slabs() * (9 * 1024 + 32); }
-
-// The two halves separately (a caller may run the weight gradient on another stream: nothing but the step's final slab
-// reduction waits for it) ...
-extern "C" int as_conv32_wino_bwd_data(const float* g_a, const float* z, const as_pcl* g, const as_conv_shape* s,
-                                       const float* wino_wt, const float* scale, const float* shift, const float* mean,
-                                       const float* coef, float slope, const float* next_z, const float* next_scale,
-                                       const float* next_shift, const float* next_mean, float* g_z, float* g_x,
-                                       float* next_bn_workspace, void* stream) {
-  if (int e = check_conv(g, g, s, "as_conv32_wino_bwd_data")) return e;
-  AS_CHECK_ARG(g_a && z && wino_wt && scale && shift && mean && coef && next_z && next_scale && next_shift && next_mean && g_z &&
-               g_x && next_bn_workspace, "as_conv32_wino_bwd_data: null pointer");
-  AS_CHECK_ARG(conv32_wino_applicable(g, g, s), "as_conv32_wino_bwd_data: configuration not supported (as_conv32_wino_ok() == 0)");
-  AS_CHECK_ARG(((uintptr_t)next_bn_workspace & 7) == 0, "as_conv32_wino_bwd_data: the BatchNorm workspace must be 8-byte aligned");
-  AS_CHECK_ARG(slope > 0.f && slope < 1.f, "as_conv32_wino_bwd_data: slope must lie in (0, 1)");
-  AS_CHECK_ARG(g_x != g_a && g_x != z && g_z != g_a && g_z != z && g_z != g_x && g_z != next_z && g_x != next_z,
-               "as_conv32_wino_bwd_data: outputs must not alias inputs or each other");
-  hipStream_t st = (hipStream_t)stream;
-  // (ALGORITHMIC flops of the gradient in its direct form, as as_conv32_bwd_fused counts them)
-  as_prof_mark(AS_PROF_WINO_DGRAD, st, 1, 0.0);
-  if (conv32_wino_dgrad2_parts() != conv32_wino_dgrad_parts()) { as_set_error("as_conv32_wino_bwd_data: partial counts differ"); return AS_ERR_ARG; }
-  // (generation 2 wins for dilation 1, 2, 4 — 286 / 269 / 268 us against 343 / 300 / 287 at 4 pairs — and loses at 8, where
-  //  only one of its three raw-row slots fits the LDS: 335 against 288; profiles/r04_b_dgrad_generations.txt)
-  const bool gen2 = g_wino_dgrad_generation == 3 || (g_wino_dgrad_generation == 2 && s->dil <= 4);
-  if (int e = (gen2 ? conv32_wino_dgrad2_launch : conv32_wino_dgrad_launch)(
-          g_a, z, g, s, wino_wt, scale, shift, mean, coef, slope, next_z, next_scale, next_shift, next_mean, g_z, g_x,
-          reinterpret_cast<double*>(next_bn_workspace), stream)) return e;
-  as_prof_mark(AS_PROF_WINO_DGRAD, st, 0, 2.0 * (double)g->B * g->H * g->W * 1024.0 * 9);
-  AS_CHECK_LAUNCH("as_conv32_wino_bwd_data");
-  return AS_OK;
-}
-
-extern "C" int as_conv32_wino_bwd_filter(const float* x, const float* g_z, const as_pcl* g, const as_conv_shape* s, float* dW,
-                                         float* db, int accumulate, float* workspace, void* stream) {
-  if (int e = check_conv(g, g, s, "as_conv32_wino_bwd_filter")) return e;
-  AS_CHECK_ARG(x && g_z && dW && workspace, "as_conv32_wino_bwd_filter: null pointer");
-  AS_CHECK_ARG(conv32_wino_applicable(g, g, s), "as_conv32_wino_bwd_filter: configuration not supported (as_conv32_wino_ok() == 0)");
-  const int T = 9;
-  const int slabs = conv32_wino_wgrad_slabs();
-  float* partial_db = workspace + (int64_t)slabs * T * 1024;
-  hipStream_t st = (hipStream_t)stream;
-  as_prof_mark(AS_PROF_WINO_WGRAD, st, 1, 0.0);
-  if (int e = conv32_wino_wgrad_launch(x, g_z, g, s, workspace, partial_db, stream)) return e;
-  as_prof_mark(AS_PROF_WINO_WGRAD, st, 0, 2.0 * (double)g->B * g->H * g->W * 1024.0 * T);
-  AS_CHECK_LAUNCH("as_conv32_wino_bwd_filter");
-  wgrad_reduce(st, workspace, partial_db, slabs, T, dW, db, accumulate);
-  AS_CHECK_LAUNCH("as_conv32_wino_bwd_filter(reduce)");
-  return AS_OK;
-}
-
-// ... and both on one stream
-extern "C" int as_conv32_wino_bwd(const float* x, const as_pcl* gin, const float* g_a, const float* z, const as_pcl* gout,
-                                  const as_conv_shape* s, const float* wino_wt, const float* scale, const float* shift,
-                                  const float* mean, const float* coef, float slope, const float* next_z,
-                                  const float* next_scale, const float* next_shift, const float* next_mean, float* g_z,
-                                  float* g_x, float* dW, float* db, int accumulate, float* next_bn_workspace,
-                                  float* workspace, void* stream) {
-  if (int e = check_conv(gin, gout, s, "as_conv32_wino_bwd")) return e;
-  AS_CHECK_ARG(x && dW && workspace, "as_conv32_wino_bwd: null pointer");
-  // (both launches below take gout alone: x laid out in another padded geometry would be read with the wrong strides)
-  AS_CHECK_ARG(conv32_wino_applicable(gin, gout, s), "as_conv32_wino_bwd: configuration not supported (as_conv32_wino_ok() == 0)");
-  AS_CHECK_ARG(g_x != x && g_z != x, "as_conv32_wino_bwd: outputs must not alias inputs or each other");
-  if (int e = as_conv32_wino_bwd_data(g_a, z, gout, s, wino_wt, scale, shift, mean, coef, slope, next_z, next_scale, next_shift,
-                                      next_mean, g_z, g_x, next_bn_workspace, stream)) return e;
-  return as_conv32_wino_bwd_filter(x, g_z, gout, s, dW, db, accumulate, workspace, stream);
-}
-
-// The same backward in ONE launch (csrc/conv32_wino_bwd.hip): data gradient and weight gradient side by side in an 8-wave
-// workgroup per CU; g_z = stage 3 of the BatchNorm backward never leaves the chip (5 tensor passes instead of 7).  Arguments of
-// as_conv32_wino_bwd without g_z; g_x bit-identical to the two-launch form.
-extern "C" int as_conv32_wino_bwd_fused_parts(void) { return conv32_wino_bwd_fused_parts(); }
-extern "C" int64_t as_conv32_wino_bwd_fused_workspace(void) { return (int64_t)conv32_wino_bwd_fused_parts() * (9 * 1024 + 32); }
-extern "C" int as_conv32_wino_bwd_fused(const float* x, const as_pcl* gin, const float* g_a, const float* z, const as_pcl* gout,
-                                        const as_conv_shape* s, const float* wino_wt, const float* scale, const float* shift,
-                                        const float* mean, const float* coef, float slope, const float* next_z,
-                                        const float* next_scale, const float* next_shift, const float* next_mean, float* g_x,
-                                        float* dW, float* db, int accumulate, float* next_bn_workspace, float* workspace,
-                                        void* stream) {
-  if (int e = check_conv(gin, gout, s, "as_conv32_wino_bwd_fused")) return e;
-  AS_CHECK_ARG(x && g_a && z && wino_wt && scale && shift && mean && coef && next_z && next_scale && next_shift && next_mean &&
-               g_x && dW && next_bn_workspace && workspace, "as_conv32_wino_bwd_fused: null pointer");
-  AS_CHECK_ARG(conv32_wino_applicable(gin, gout, s), "as_conv32_wino_bwd_fused: configuration not supported (as_conv32_wino_ok() == 0)");
-  AS_CHECK_ARG(((uintptr_t)next_bn_workspace & 7) == 0, "as_conv32_wino_bwd_fused: the BatchNorm workspace must be 8-byte aligned");
-  AS_CHECK_ARG(slope > 0.f && slope < 1.f, "as_conv32_wino_bwd_fused: slope must lie in (0, 1)");
-  AS_CHECK_ARG(g_x != g_a && g_x != z && g_x != x && g_x != next_z, "as_conv32_wino_bwd_fused: g_x must not alias an input");
-  const int T = 9;
-  const int slabs = conv32_wino_bwd_fused_parts();
-  float* partial_db = workspace + (int64_t)slabs * T * 1024;
-  hipStream_t st = (hipStream_t)stream;
-  as_prof_mark(AS_PROF_WINO_BWD, st, 1, 0.0);
-  if (int e = conv32_wino_bwd_fused_launch(x, g_a, z, gout, s, wino_wt, scale, shift, mean, coef, slope, next_z, next_scale, next_shift,
-                                           next_mean, g_x, workspace, partial_db, reinterpret_cast<double*>(next_bn_workspace),
-                                           stream)) return e;
-  as_prof_mark(AS_PROF_WINO_BWD, st, 0, 2.0 * 2.0 * (double)gout->B * gout->H * gout->W * 1024.0 * T);   // dgrad + wgrad, direct form
-  AS_CHECK_LAUNCH("as_conv32_wino_bwd_fused");
-  wgrad_reduce(st, workspace, partial_db, slabs, T, dW, db, accumulate);
-  AS_CHECK_LAUNCH("as_conv32_wino_bwd_fused(reduce)");
   return AS_OK;
 }
 

@@ -138,17 +138,12 @@ bool conv32_s2_fwd_applicable(const as_pcl* gin, const as_pcl* gout, const as_co
 int conv32_s2_fwd_launch(const float* x, const as_pcl* gin, const float* packed_w, const float* bias, float* z,
                          const as_pcl* gout, void* stream) {
   static AsPerDevice attr_set;
-  if (!attr_set.get()) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv32_s2_fwd_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 4 * S2F_WAVE);
-    if (e != hipSuccess) { as_set_error("as_conv32_fwd: %s", hipGetErrorString(e)); return AS_ERR_LAUNCH; }
-    attr_set.set();
-  }
   S2Args a;
   a.x = x; a.wp = packed_w; a.bias = bias; a.out = z; a.gin = as_make_dev(gin); a.gout = as_make_dev(gout);
   a.nseg = (gout->W + 31) / 32; a.ntiles = gout->B * gout->H * a.nseg;
-  hipLaunchKernelGGL(conv32_s2_fwd_kernel, dim3(as_div_up(a.ntiles, 4)), dim3(256), 4 * S2F_WAVE, (hipStream_t)stream, a);
-  return AS_OK;
+  void* kargs[] = {&a};
+  return as_launch_lds(reinterpret_cast<const void*>(conv32_s2_fwd_kernel), attr_set, 4 * S2F_WAVE, 4 * S2F_WAVE,
+                       dim3(as_div_up(a.ntiles, 4)), dim3(256), kargs, "as_conv32_fwd", (hipStream_t)stream);
 }
 
 // ---- data gradient: gx[2y'+py][2x'+px] from gz rows y'-1 .. y'+1 -------------------------------------------------------
@@ -237,15 +232,10 @@ bool conv32_s2_dgrad_applicable(const as_pcl* ggz, const as_pcl* ggx) {
 
 int conv32_s2_dgrad_launch(const float* gz, const as_pcl* ggz, const float* packed, float* gx, const as_pcl* ggx, void* stream) {
   static AsPerDevice attr_set;
-  if (!attr_set.get()) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv32_s2_dgrad_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 4 * S2D_WAVE);
-    if (e != hipSuccess) { as_set_error("as_conv32_dgrad_s2: %s", hipGetErrorString(e)); return AS_ERR_LAUNCH; }
-    attr_set.set();
-  }
   S2Args a;
   a.x = gz; a.wp = packed; a.bias = nullptr; a.out = gx; a.gin = as_make_dev(ggz); a.gout = as_make_dev(ggx);
   a.nseg = (ggz->W + 31) / 32; a.ntiles = ggz->B * ggz->H * a.nseg;
-  hipLaunchKernelGGL(conv32_s2_dgrad_kernel, dim3(as_div_up(a.ntiles, 4)), dim3(256), 4 * S2D_WAVE, (hipStream_t)stream, a);
-  return AS_OK;
+  void* kargs[] = {&a};
+  return as_launch_lds(reinterpret_cast<const void*>(conv32_s2_dgrad_kernel), attr_set, 4 * S2D_WAVE, 4 * S2D_WAVE,
+                       dim3(as_div_up(a.ntiles, 4)), dim3(256), kargs, "as_conv32_dgrad_s2", (hipStream_t)stream);
 }

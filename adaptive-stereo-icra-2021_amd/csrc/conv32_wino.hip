@@ -35,7 +35,7 @@
 // operands the outputs are closer than the direct kernels' (tests/test_gpu_kernels.py holds them to "not further than 2x").
 #include "as_common.h"
 #include "conv_epilogue.h"
-#include "conv32_wino.h"
+#include "conv32_layer.h"
 #include "conv32_wino_dev.h"
 #ifndef WN_OLD_T
 #define WN_OLD_T 0
@@ -82,8 +82,6 @@ struct WinoArgs {
 // Diagnostic build (make EXTRA=-DWN_TIMING_BUILD): every wave adds up the shader cycles it spends in each phase; a launch
 // with AS_WN_TIMING set dumps them to gpurun_out/wino_timing.bin (tests/tools/wino_microbench.py prints the averages).
 #ifdef WN_TIMING_BUILD
-#include <cstdio>
-#include <cstdlib>
 #define WN_T(slot) do { const long long now_ = clock64(); tacc[slot] += now_ - tlast; tlast = now_; } while (0)
 #else
 #define WN_T(slot) do { } while (0)
@@ -584,24 +582,18 @@ __global__ __launch_bounds__(256, WN_WGS_PER_CU(MODE)) void conv32_wino_kernel(W
 }
 
 static int wn_grid(int mode) { return WN_GRID / (2 / WN_WGS_PER_CU(mode)); }
-static int wn_log2(int d) { return d == 1 ? 0 : d == 2 ? 1 : d == 4 ? 2 : d == 8 ? 3 : -1; }
-
-static long wn_pairs(int H, int d) {
-  long n = 0;
-  for (int r = 0; r < d; ++r) n += ((H - r + d - 1) / d + 1) / 2;
-  return n;
-}
 
 // Applicable to the refinement geometry: 2-D 3x3 stride 1, dilation 1/2/4/8 within the halo, rows of at least 64 pixels and
 // enough row pairs for the fixed grid.
 bool conv32_wino_applicable(const as_pcl* gin, const as_pcl* gout, const as_conv_shape* s) {
+  const WinoTiling t = wino_tiling(gout, s);
   if (s->kd != 1 || s->kh != 3 || s->kw != 3 || s->stride != 1) return false;
-  if (wn_log2(s->dil) < 0 || s->pad_h != s->dil || s->pad_w != s->dil) return false;
+  if (t.L < 0 || s->pad_h != s->dil || s->pad_w != s->dil) return false;
   if (gin->D != 1 || gout->D != 1 || gin->pd != 0) return false;
   if (gin->B != gout->B || gin->H != gout->H || gin->W != gout->W) return false;
   if (gin->ph != gout->ph || gin->pw != gout->pw || gin->pw < 8 || gin->ph < s->dil) return false;
   if (gout->W < WN_SEG || gout->H < 2 * s->dil) return false;
-  const long units = (long)gout->B * ((gout->W + WN_SEG - 1) / WN_SEG) * wn_pairs(gout->H, s->dil);
+  const long units = (long)gout->B * t.nseg * t.pairs;
   return units >= 4L * WN_GRID && units < (1L << 31);
 }
 
@@ -609,38 +601,27 @@ int conv32_wino_parts(void) { return WN_GRID; }
 int conv32_wino_dgrad_parts(void) { return wn_grid(2); }
 
 template <int MODE> static const void* wn_kernel(int L) {
-  switch (L) {
-    case 0: return reinterpret_cast<const void*>(conv32_wino_kernel<MODE, 0>);
-    case 1: return reinterpret_cast<const void*>(conv32_wino_kernel<MODE, 1>);
-    case 2: return reinterpret_cast<const void*>(conv32_wino_kernel<MODE, 2>);
-    default: return reinterpret_cast<const void*>(conv32_wino_kernel<MODE, 3>);
-  }
+  return wino_by_L(L, [](auto l) { return reinterpret_cast<const void*>(conv32_wino_kernel<MODE, decltype(l)::value>); });
 }
 
-static int wn_launch(int mode, int L, const WinoArgs& a, const char* who, void* stream) {
+// a.nseg, a.pairs and the instantiation come from the tiling here
+static int wn_launch(int mode, WinoArgs a, const as_pcl* g, const as_conv_shape* s, const char* who, void* stream) {
   static AsPerDevice attr_set[16];
-  const void* fn = mode == 3 ? wn_kernel<3>(L) : (mode == 2 ? wn_kernel<2>(L) : (mode == 1 ? wn_kernel<1>(L) : wn_kernel<0>(L)));
-  const int fi = mode * 4 + L;
-  if (!attr_set[fi].get()) {
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, WN_LDS_BYTES);
-    if (e != hipSuccess) { as_set_error("%s: %s", who, hipGetErrorString(e)); return AS_ERR_LAUNCH; }
-    attr_set[fi].set();
-  }
-  WinoArgs args = a;
+  static_assert(WN_SEG == 64, "wino_tiling cuts rows into segments of 64");
+  const WinoTiling t = wino_tiling(g, s);
+  const void* fn = mode == 3 ? wn_kernel<3>(t.L) : (mode == 2 ? wn_kernel<2>(t.L) : (mode == 1 ? wn_kernel<1>(t.L) : wn_kernel<0>(t.L)));
+  a.g = as_make_dev(g);
+  a.nseg = t.nseg; a.pairs = t.pairs;
 #ifdef WN_TIMING_BUILD
   static long long* timing_buf = nullptr;
   const size_t timing_bytes = (size_t)WN_GRID * 4 * 12 * 8;
-  if (!timing_buf) hipMalloc(&timing_buf, timing_bytes);
-  hipMemsetAsync(timing_buf, 0, timing_bytes, (hipStream_t)stream);
-  args.timing = timing_buf;
+  a.timing = as_timing_begin(timing_buf, timing_bytes, (hipStream_t)stream);
 #endif
-  void* kargs[] = {&args};
-  hipError_t le = hipLaunchKernel(fn, dim3(wn_grid(mode)), dim3(256), kargs, WN_LDS_BYTES, (hipStream_t)stream);
-  if (le != hipSuccess) { as_set_error("%s: launch failed: %s", who, hipGetErrorString(le)); return AS_ERR_LAUNCH; }
+  void* kargs[] = {&a};
+  if (int e = as_launch_lds(fn, attr_set[mode * 4 + t.L], WN_LDS_BYTES, WN_LDS_BYTES, dim3(wn_grid(mode)), dim3(256), kargs, who,
+                            (hipStream_t)stream)) return e;
 #ifdef WN_TIMING_BUILD
-  if (getenv("AS_WN_TIMING")) {                            // dump THIS launch (synchronises: diagnostic build only)
-    hipStreamSynchronize((hipStream_t)stream);
-    void* hbuf = malloc(timing_bytes); hipMemcpy(hbuf, timing_buf, timing_bytes, hipMemcpyDeviceToHost);
+  if (void* hbuf = as_timing_fetch("AS_WN_TIMING", timing_buf, timing_bytes, (hipStream_t)stream)) {   // dump THIS launch
     char name[128]; snprintf(name, sizeof name, "gpurun_out/wino_timing_m%d.bin", mode);
     FILE* f = fopen(name, "wb"); if (f) { fwrite(hbuf, 1, timing_bytes, f); fclose(f); } free(hbuf);
   }
@@ -648,41 +629,34 @@ static int wn_launch(int mode, int L, const WinoArgs& a, const char* who, void* 
   return AS_OK;
 }
 
-int conv32_wino_launch(const float* z_prev, const float* a_prevprev, const float* in_scale, const float* in_shift, float* a_out,
-                       const as_pcl* g, const as_conv_shape* s, const float* wino_w, const float* bias, float slope,
-                       float* z, float* stat_mean, float* stat_m2, float* stat_cnt, void* stream) {
+int conv32_wino_launch(const LayerFwdArgs& f, const as_pcl* g, const as_conv_shape* s, const char* who, void* stream) {
   WinoArgs a = {};
-  a.zin = z_prev; a.ain = a_prevprev; a.in_scale = in_scale; a.in_shift = in_shift; a.a_out = a_out; a.wq = wino_w;
-  a.ep.bias = bias; a.ep.z = z; a.ep.ep_scale = nullptr; a.ep.ep_shift = nullptr; a.ep.residual = nullptr;
-  a.ep.stat_mean = stat_mean; a.ep.stat_m2 = stat_m2; a.ep.stat_cnt = stat_cnt; a.ep.epilogue = 0; a.ep.slope = slope;
-  a.g = as_make_dev(g);
-  a.nseg = (g->W + WN_SEG - 1) / WN_SEG; a.pairs = (int)wn_pairs(g->H, s->dil); a.slope = slope;
-  return wn_launch(a_prevprev != nullptr ? 1 : 0, wn_log2(s->dil), a, "as_conv32_wino_fwd", stream);
+  a.zin = f.z_prev; a.ain = f.a_prevprev; a.in_scale = f.in_scale; a.in_shift = f.in_shift; a.a_out = f.a_out; a.wq = f.w;
+  a.ep.bias = f.bias; a.ep.z = f.z; a.ep.ep_scale = nullptr; a.ep.ep_shift = nullptr; a.ep.residual = nullptr;
+  a.ep.stat_mean = f.stat_mean; a.ep.stat_m2 = f.stat_m2; a.ep.stat_cnt = f.stat_cnt; a.ep.epilogue = 0; a.ep.slope = f.slope;
+  a.slope = f.slope;
+  return wn_launch(f.a_prevprev != nullptr ? 1 : 0, a, g, s, who, stream);
 }
 
 // Eval forward (MODE 3): out = lrelu((conv(x) + bias) * scale + shift) (+ x if residual).
 int conv32_wino_eval_launch(const float* x, const as_pcl* g, const as_conv_shape* s, const float* wino_w, const float* bias,
-                            const float* scale, const float* shift, float slope, int residual, float* out, void* stream) {
+                            const float* scale, const float* shift, float slope, int residual, float* out, const char* who,
+                            void* stream) {
   WinoArgs a = {};
   a.zin = x; a.wq = wino_w;
   a.ep.bias = bias; a.ep.z = out; a.ep.ep_scale = scale; a.ep.ep_shift = shift; a.ep.residual = residual ? x : nullptr;
   a.ep.epilogue = 1; a.ep.slope = slope;
-  a.g = as_make_dev(g);
-  a.nseg = (g->W + WN_SEG - 1) / WN_SEG; a.pairs = (int)wn_pairs(g->H, s->dil); a.slope = slope;
-  return wn_launch(3, wn_log2(s->dil), a, "as_conv32_wino_eval", stream);
+  a.slope = slope;
+  return wn_launch(3, a, g, s, who, stream);
 }
 
 // Data gradient of the layer (MODE 2): g_z (by-product), g_x = dgrad(g_z) + g_a, next-BatchNorm sums [WN_GRID][64].
-int conv32_wino_dgrad_launch(const float* g_a, const float* z, const as_pcl* g, const as_conv_shape* s, const float* wino_wt,
-                             const float* scale, const float* shift, const float* mean, const float* coef, float slope,
-                             const float* next_z, const float* next_scale, const float* next_shift, const float* next_mean,
-                             float* g_z, float* g_x, double* next_partial, void* stream) {
+int conv32_wino_dgrad_launch(const LayerBwdArgs& b, const as_pcl* g, const as_conv_shape* s, const char* who, void* stream) {
   WinoArgs a = {};
-  a.zin = z; a.ain = g_a; a.in_scale = scale; a.in_shift = shift; a.a_out = g_z; a.wq = wino_wt;
-  a.ep.z = g_x; a.ep.slope = slope;
-  a.g = as_make_dev(g);
-  a.nseg = (g->W + WN_SEG - 1) / WN_SEG; a.pairs = (int)wn_pairs(g->H, s->dil); a.slope = slope;
-  a.bn_mean = mean; a.bn_coef = coef; a.nz = next_z; a.n_scale = next_scale; a.n_shift = next_shift; a.n_mean = next_mean;
-  a.n_partial = next_partial;
-  return wn_launch(2, wn_log2(s->dil), a, "as_conv32_wino_bwd", stream);
+  a.zin = b.z; a.ain = b.g_a; a.in_scale = b.scale; a.in_shift = b.shift; a.a_out = b.g_z; a.wq = b.w;
+  a.ep.z = b.g_x; a.ep.slope = b.slope;
+  a.slope = b.slope;
+  a.bn_mean = b.mean; a.bn_coef = b.coef; a.nz = b.next_z; a.n_scale = b.next_scale; a.n_shift = b.next_shift; a.n_mean = b.next_mean;
+  a.n_partial = b.next_partial;
+  return wn_launch(2, a, g, s, who, stream);
 }

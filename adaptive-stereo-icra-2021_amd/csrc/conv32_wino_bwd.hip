@@ -31,13 +31,9 @@
 // g_x and the next BatchNorm's partial sums are those of the two-launch form bit for bit per element / equal to rounding per
 // partial (256 workgroups here, 512 there); dW differs from conv32_wino_wgrad.hip's by the order of the sum over tiles only.
 #include "as_common.h"
-#include "conv32_wino.h"
+#include "conv32_layer.h"
 #include "conv32_wino_dev.h"
 #include "conv32_wino_dgrad_role.h"
-#ifdef FB_TIMING_BUILD
-#include <cstdio>
-#include <cstdlib>
-#endif
 
 #ifndef FB_GRID
 #define FB_GRID 256
@@ -73,14 +69,6 @@ __device__ inline void fb_dma_1kb(const float* sbase, unsigned voff, unsigned m0
   asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" :: "s"(m0), "v"(voff), "s"(sbase) : "memory", "m0");
 }
 
-// staged voxel (80-voxel frame of wn_addr) -> LDS position, and swizzle key, as compile-time constants
-template <int L> __host__ __device__ constexpr int fb_pos(int v) { return L == 0 ? ((v & ~3) | ((v & 1) << 1) | ((v >> 1) & 1)) : v; }
-template <int L> __host__ __device__ constexpr int fb_swz(int v) {
-  const int w = v + 8;
-  const int key = ((w >> (L + 1)) << L) | (w & ((1 << L) - 1));
-  return (key >> 1) & 7;
-}
-
 // The sixteen matrix steps of one tile (rows j, j+1 of g_z; rows j-1 .. j+2 of x) for the wave that owns row RW of the transformed
 // tiles.  Step s takes tiles s (lanes 0-31) and s + 16 (lanes 32-63: 32 voxels further in both rings, the same swizzle key).
 // MASKED: g_z values of columns >= keep are not this segment's (kh = keep - 32 * half).
@@ -101,7 +89,7 @@ __device__ __forceinline__ void fb_w_steps(f32x16 (&acc)[4], float& bsum, const 
 #pragma unroll
     for (int jc = 0; jc < 2; ++jc) {
       const int v = 8 + c0 + jc * d;
-      const int S = fb_swz<L>(v), off = (fb_pos<L>(v) - G::V0) * 128;
+      const int S = wn_swz<L>(v), off = (wn_pos<L>(v) - G::V0) * 128;
       if (RW != 3) g0[jc] = *reinterpret_cast<const float*>(smem + g0_base[S] + off);
       if (RW != 0) g1[jc] = *reinterpret_cast<const float*>(smem + g1_base[S] + off);
       if constexpr (MASKED) {
@@ -313,48 +301,28 @@ __global__ __launch_bounds__(512, 1) void conv32_wino_bwd_kernel(FusedBwdArgs q)
 
 int conv32_wino_bwd_fused_parts(void) { return FB_GRID; }
 
-int conv32_wino_bwd_fused_launch(const float* x, const float* g_a, const float* z, const as_pcl* g, const as_conv_shape* s,
-                                 const float* wino_wt, const float* scale, const float* shift, const float* mean, const float* coef,
-                                 float slope, const float* next_z, const float* next_scale, const float* next_shift,
-                                 const float* next_mean, float* g_x, float* partial, float* partial_db, double* next_partial,
-                                 void* stream) {
+int conv32_wino_bwd_fused_launch(const LayerBwdArgs& b, const as_pcl* g, const as_conv_shape* s, const char* who, void* stream) {
   static AsPerDevice attr_set[4];
-  const int L = s->dil == 1 ? 0 : (s->dil == 2 ? 1 : (s->dil == 4 ? 2 : 3));
-  const void* fn = L == 0 ? reinterpret_cast<const void*>(conv32_wino_bwd_kernel<0>)
-                 : L == 1 ? reinterpret_cast<const void*>(conv32_wino_bwd_kernel<1>)
-                 : L == 2 ? reinterpret_cast<const void*>(conv32_wino_bwd_kernel<2>)
-                          : reinterpret_cast<const void*>(conv32_wino_bwd_kernel<3>);
-  const int lds = L == 0 ? FbGeo<0>::LDS : (L == 1 ? FbGeo<1>::LDS : (L == 2 ? FbGeo<2>::LDS : FbGeo<3>::LDS));
   static_assert(FbGeo<3>::LDS <= 163840 && FbGeo<0>::LDS <= 163840, "one workgroup per CU");
-  if (!attr_set[L].get()) {
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) { as_set_error("as_conv32_wino_bwd_fused: %s", hipGetErrorString(e)); return AS_ERR_LAUNCH; }
-    attr_set[L].set();
-  }
+  const WinoTiling t = wino_tiling(g, s);
+  const WinoKernel k = wino_by_L(t.L, [](auto l) {
+    constexpr int L = decltype(l)::value;
+    return WinoKernel{reinterpret_cast<const void*>(conv32_wino_bwd_kernel<L>), FbGeo<L>::LDS};
+  });
   FusedBwdArgs a;
-  a.dg.z = z; a.dg.g_a = g_a; a.dg.g_z = nullptr; a.dg.g_x = g_x; a.dg.wq = wino_wt;
-  a.dg.in_scale = scale; a.dg.in_shift = shift; a.dg.bn_mean = mean; a.dg.bn_coef = coef;
-  a.dg.nz = next_z; a.dg.n_scale = next_scale; a.dg.n_shift = next_shift; a.dg.n_mean = next_mean; a.dg.n_partial = next_partial;
-  a.dg.g = as_make_dev(g);
-  a.dg.nseg = (g->W + 63) / 64;
-  long pairs = 0;
-  for (int r = 0; r < s->dil; ++r) pairs += ((g->H - r + s->dil - 1) / s->dil + 1) / 2;
-  a.dg.pairs = (int)pairs; a.dg.slope = slope;
-  a.x = x; a.partial = partial; a.partial_db = partial_db;
+  a.dg = dgrad_args(b, g, t);
+  a.dg.g_z = nullptr;
+  a.x = b.x; a.partial = b.partial; a.partial_db = b.partial_db;
 #ifdef FB_TIMING_BUILD
   static long long* timing_buf = nullptr;
   const size_t timing_bytes = (size_t)FB_GRID * 8 * 10 * 8;
-  if (!timing_buf) (void)hipMalloc(&timing_buf, timing_bytes);
-  (void)hipMemsetAsync(timing_buf, 0, timing_bytes, (hipStream_t)stream);
-  a.dg.timing = timing_buf;
+  a.dg.timing = as_timing_begin(timing_buf, timing_bytes, (hipStream_t)stream);
 #endif
   void* kargs[] = {&a};
-  hipError_t le = hipLaunchKernel(fn, dim3(FB_GRID), dim3(512), kargs, lds, (hipStream_t)stream);
-  if (le != hipSuccess) { as_set_error("as_conv32_wino_bwd_fused: launch failed: %s", hipGetErrorString(le)); return AS_ERR_LAUNCH; }
+  if (int e = as_launch_lds(k.fn, attr_set[t.L], k.lds_bytes, k.lds_bytes, dim3(FB_GRID), dim3(512), kargs, who, (hipStream_t)stream))
+    return e;
 #ifdef FB_TIMING_BUILD
-  if (getenv("AS_FB_TIMING")) {                            // dump THIS launch (synchronises: diagnostic build only)
-    (void)hipStreamSynchronize((hipStream_t)stream);
-    void* hbuf = malloc(timing_bytes); (void)hipMemcpy(hbuf, timing_buf, timing_bytes, hipMemcpyDeviceToHost);
+  if (void* hbuf = as_timing_fetch("AS_FB_TIMING", timing_buf, timing_bytes, (hipStream_t)stream)) {   // dump THIS launch
     FILE* f = fopen("gpurun_out/fused_bwd_timing.bin", "wb"); if (f) { fwrite(hbuf, 1, timing_bytes, f); fclose(f); } free(hbuf);
   }
 #endif

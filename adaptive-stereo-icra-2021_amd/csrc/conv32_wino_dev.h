@@ -20,9 +20,9 @@ template <int IMM> __device__ inline void wn_store_imm(float* sbase, unsigned vo
 
 // first column (relative to the segment) of tile t at dilation 2^L: blocks of 2d columns hold d tiles
 template <int L> __host__ __device__ constexpr int wn_c0(int t) { return ((t >> L) << (L + 1)) | (t & ((1 << L) - 1)); }
-// LDS position and swizzle of staged voxel v (0..79)
-template <int L> __device__ inline int wn_pos(int v) { return L == 0 ? ((v & ~3) | ((v & 1) << 1) | ((v >> 1) & 1)) : v; }
-template <int L> __device__ inline int wn_swz(int v) {
+// LDS position and swizzle key of staged voxel v (0..79); compile-time constants where v is one
+template <int L> __host__ __device__ constexpr int wn_pos(int v) { return L == 0 ? ((v & ~3) | ((v & 1) << 1) | ((v >> 1) & 1)) : v; }
+template <int L> __host__ __device__ constexpr int wn_swz(int v) {
   const int w = v + 8;
   const int key = ((w >> (L + 1)) << L) | (w & ((1 << L) - 1));
   return (key >> 1) & 7;

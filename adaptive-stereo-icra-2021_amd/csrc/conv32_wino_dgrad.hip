@@ -32,7 +32,7 @@
 // Bit-identical to the first generation (tests/test_gpu_kernels.py: g_z, g_x and the next-BatchNorm partials against
 // conv32_wino_kernel<2, L>): same element-wise chains, same order in every sum, the same ownership of shared columns.
 #include "as_common.h"
-#include "conv32_wino.h"
+#include "conv32_layer.h"
 #include "conv32_wino_dev.h"
 #include "conv32_wino_dgrad_role.h"
 
@@ -63,33 +63,14 @@ __global__ __launch_bounds__(256, 2) void conv32_wino_dgrad_kernel(DgradArgs p) 
 
 int conv32_wino_dgrad2_parts(void) { return DG_GRID; }
 
-int conv32_wino_dgrad2_launch(const float* g_a, const float* z, const as_pcl* g, const as_conv_shape* s, const float* wino_wt,
-                              const float* scale, const float* shift, const float* mean, const float* coef, float slope,
-                              const float* next_z, const float* next_scale, const float* next_shift, const float* next_mean,
-                              float* g_z, float* g_x, double* next_partial, void* stream) {
+int conv32_wino_dgrad2_launch(const LayerBwdArgs& b, const as_pcl* g, const as_conv_shape* s, const char* who, void* stream) {
   static AsPerDevice attr_set[4];
-  const int L = s->dil == 1 ? 0 : (s->dil == 2 ? 1 : (s->dil == 4 ? 2 : 3));
-  const void* fn = L == 0 ? reinterpret_cast<const void*>(conv32_wino_dgrad_kernel<0>)
-                 : L == 1 ? reinterpret_cast<const void*>(conv32_wino_dgrad_kernel<1>)
-                 : L == 2 ? reinterpret_cast<const void*>(conv32_wino_dgrad_kernel<2>)
-                          : reinterpret_cast<const void*>(conv32_wino_dgrad_kernel<3>);
-  const int lds = L == 0 ? DgGeo<0>::LDS : (L == 1 ? DgGeo<1>::LDS : (L == 2 ? DgGeo<2>::LDS : DgGeo<3>::LDS));
-  if (!attr_set[L].get()) {
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) { as_set_error("as_conv32_wino_bwd_data: %s", hipGetErrorString(e)); return AS_ERR_LAUNCH; }
-    attr_set[L].set();
-  }
-  DgradArgs a;
-  a.z = z; a.g_a = g_a; a.g_z = g_z; a.g_x = g_x; a.wq = wino_wt;
-  a.in_scale = scale; a.in_shift = shift; a.bn_mean = mean; a.bn_coef = coef;
-  a.nz = next_z; a.n_scale = next_scale; a.n_shift = next_shift; a.n_mean = next_mean; a.n_partial = next_partial;
-  a.g = as_make_dev(g);
-  a.nseg = (g->W + 63) / 64;
-  long pairs = 0;
-  for (int r = 0; r < s->dil; ++r) pairs += ((g->H - r + s->dil - 1) / s->dil + 1) / 2;
-  a.pairs = (int)pairs; a.slope = slope;
+  const WinoTiling t = wino_tiling(g, s);
+  const WinoKernel k = wino_by_L(t.L, [](auto l) {
+    constexpr int L = decltype(l)::value;
+    return WinoKernel{reinterpret_cast<const void*>(conv32_wino_dgrad_kernel<L>), DgGeo<L>::LDS};
+  });
+  DgradArgs a = dgrad_args(b, g, t);
   void* kargs[] = {&a};
-  hipError_t le = hipLaunchKernel(fn, dim3(DG_GRID), dim3(256), kargs, lds, (hipStream_t)stream);
-  if (le != hipSuccess) { as_set_error("as_conv32_wino_bwd_data: launch failed: %s", hipGetErrorString(le)); return AS_ERR_LAUNCH; }
-  return AS_OK;
+  return as_launch_lds(k.fn, attr_set[t.L], k.lds_bytes, k.lds_bytes, dim3(DG_GRID), dim3(256), kargs, who, (hipStream_t)stream);
 }

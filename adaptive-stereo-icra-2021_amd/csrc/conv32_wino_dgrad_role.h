@@ -3,7 +3,7 @@
 // beside four weight-gradient waves in one launch (FUSED).
 #pragma once
 #include "as_common.h"
-#include "conv32_wino.h"
+#include "conv32_layer.h"
 #include "conv32_wino_dev.h"
 
 // build-time switches of the FUSED flavour (tests/tools/fused_bwd_ab.sh times every combination on one box)
@@ -63,6 +63,16 @@ struct DgradArgs {
   long long* timing;       // diagnostic build of conv32_wino_bwd.hip only: [workgroup][wave][10] cycle counts per phase
 #endif
 };
+// (the launchers of conv32_wino_dgrad.hip and conv32_wino_bwd.hip; the latter passes no g_z)
+static inline DgradArgs dgrad_args(const LayerBwdArgs& b, const as_pcl* g, const WinoTiling& t) {
+  DgradArgs a = {};
+  a.z = b.z; a.g_a = b.g_a; a.g_z = b.g_z; a.g_x = b.g_x; a.wq = b.w;
+  a.in_scale = b.scale; a.in_shift = b.shift; a.bn_mean = b.mean; a.bn_coef = b.coef;
+  a.nz = b.next_z; a.n_scale = b.next_scale; a.n_shift = b.next_shift; a.n_mean = b.next_mean; a.n_partial = b.next_partial;
+  a.g = as_make_dev(g);
+  a.nseg = t.nseg; a.pairs = t.pairs; a.slope = b.slope;
+  return a;
+}
 
 // Diagnostic build (make EXTRA=-DFB_TIMING_BUILD; tests/tools/fused_bwd_timing.py prints the averages): every wave of the fused
 // backward adds up the shader cycles it spends in each phase.  Slots: 0 decode + run-in, 1 matrix phase, 2 work up to B1,

@@ -22,7 +22,8 @@
 // they come), WW_EXP_NOMFMA (data movement only) — they gave the floors quoted in DESIGN 4: matrix work alone 121-127 us, + loads
 // +15, + transforms +15, both +55, data movement alone 100 us.
 #include "as_common.h"
-#include "conv32_wino.h"
+#include "conv32_layer.h"
+#include "conv32_wino_dev.h"
 
 #define WW_CHUNK 1152                        // 8 voxels of 128 B + one voxel of padding
 #define WW_XROW (10 * WW_CHUNK)              // 11,520: 80 staged voxels (8 + 64 + 8)
@@ -52,7 +53,6 @@ __device__ inline void ww_dma_1kb(const float* sbase, unsigned voff, unsigned m0
                :: "s"(m0), "v"(voff), "s"(sbase) : "memory", "m0");
 }
 
-template <int L> __host__ __device__ constexpr int ww_c0(int t) { return ((t >> L) << (L + 1)) | (t & ((1 << L) - 1)); }
 __host__ __device__ constexpr int ww_off(int v) { return (v >> 3) * WW_CHUNK + (v & 7) * 128; }
 // tile of matrix step s, half 0 (half 1: + 1 for d > 1, + 4 for d = 1 — a voxel in the other bank half either way)
 template <int L> __host__ __device__ constexpr int ww_tile(int s) { return L == 0 ? (s & 3) + 8 * (s >> 2) : 2 * s; }
@@ -150,13 +150,13 @@ __device__ __forceinline__ void conv32_wino_wgrad_role(const WgradWinoArgs& p, c
         const int t0 = ww_tile<L>(s);
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
-          const int off = ww_off(8 + ww_c0<L>(t0) + (m - 1) * d);
+          const int off = ww_off(8 + wn_c0<L>(t0) + (m - 1) * d);
           xa[m] = *reinterpret_cast<const float*>(xa_row + off);
           xb[m] = *reinterpret_cast<const float*>(xb_row + off);
         }
 #pragma unroll
         for (int jc = 0; jc < 2; ++jc) {
-          const int off = ww_off(ww_c0<L>(t0) + jc * d);
+          const int off = ww_off(wn_c0<L>(t0) + jc * d);
           if (RW != 3) g0[jc] = *reinterpret_cast<const float*>(g_row + off);
           if (RW != 0) g1[jc] = *reinterpret_cast<const float*>(g_row + WW_GROW + off);
         }
@@ -303,28 +303,14 @@ __global__ __launch_bounds__(512, 1) void conv32_wino_wgrad_kernel(WgradWinoArgs
 
 int conv32_wino_wgrad_slabs(void) { return WW_GRID; }
 
-int conv32_wino_wgrad_launch(const float* x, const float* g_z, const as_pcl* g, const as_conv_shape* s, float* partial,
-                             float* partial_db, void* stream) {
+int conv32_wino_wgrad_launch(const LayerBwdArgs& b, const as_pcl* g, const as_conv_shape* s, const char* who, void* stream) {
   static AsPerDevice attr_set[4];
-  const int L = s->dil == 1 ? 0 : (s->dil == 2 ? 1 : (s->dil == 4 ? 2 : 3));
-  const void* fn = L == 0 ? reinterpret_cast<const void*>(conv32_wino_wgrad_kernel<0>)
-                 : L == 1 ? reinterpret_cast<const void*>(conv32_wino_wgrad_kernel<1>)
-                 : L == 2 ? reinterpret_cast<const void*>(conv32_wino_wgrad_kernel<2>)
-                          : reinterpret_cast<const void*>(conv32_wino_wgrad_kernel<3>);
-  if (!attr_set[L].get()) {
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, WW_LDS_BYTES);
-    if (e != hipSuccess) { as_set_error("as_conv32_wino_bwd: %s", hipGetErrorString(e)); return AS_ERR_LAUNCH; }
-    attr_set[L].set();
-  }
+  const WinoTiling t = wino_tiling(g, s);
+  const void* fn = wino_by_L(t.L, [](auto l) { return reinterpret_cast<const void*>(conv32_wino_wgrad_kernel<decltype(l)::value>); });
   WgradWinoArgs a;
-  a.x = x; a.gz = g_z; a.partial = partial; a.partial_db = partial_db;
+  a.x = b.x; a.gz = b.g_z; a.partial = b.partial; a.partial_db = b.partial_db;
   a.g = as_make_dev(g);
-  a.nseg = (g->W + 63) / 64;
-  long pairs = 0;
-  for (int r = 0; r < s->dil; ++r) pairs += ((g->H - r + s->dil - 1) / s->dil + 1) / 2;
-  a.pairs = (int)pairs;
+  a.nseg = t.nseg; a.pairs = t.pairs;
   void* kargs[] = {&a};
-  hipError_t le = hipLaunchKernel(fn, dim3(WW_GRID), dim3(512), kargs, WW_LDS_BYTES, (hipStream_t)stream);
-  if (le != hipSuccess) { as_set_error("as_conv32_wino_bwd: launch failed: %s", hipGetErrorString(le)); return AS_ERR_LAUNCH; }
-  return AS_OK;
+  return as_launch_lds(fn, attr_set[t.L], WW_LDS_BYTES, WW_LDS_BYTES, dim3(WW_GRID), dim3(512), kargs, who, (hipStream_t)stream);
 }

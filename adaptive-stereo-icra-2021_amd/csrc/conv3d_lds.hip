@@ -183,15 +183,9 @@ int conv3d_lds_launch(const float* x, const as_pcl* gin, const float* packed_w, 
   a.groups = (a.run + 7) / 8;
   const int lds_bytes = a.groups * 1024;
   static AsPerDevice attr_set;
-  if (!attr_set.get()) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3d_lds_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-    if (e != hipSuccess) { as_set_error("as_conv32_fwd(3-D LDS): %s", hipGetErrorString(e)); return AS_ERR_LAUNCH; }
-    attr_set.set();
-  }
-  hipLaunchKernelGGL(conv3d_lds_kernel, dim3(conv3d_lds_grid(gout)), dim3(256), lds_bytes, (hipStream_t)stream, a);
-  AS_CHECK_LAUNCH("as_conv32_fwd(3-D LDS)");
-  return AS_OK;
+  void* kargs[] = {&a};
+  return as_launch_lds(reinterpret_cast<const void*>(conv3d_lds_kernel), attr_set, 64 * 1024, lds_bytes, dim3(conv3d_lds_grid(gout)),
+                       dim3(256), kargs, "as_conv32_fwd(3-D LDS)", (hipStream_t)stream);
 }
 
 
@@ -355,13 +349,7 @@ int conv3d_wgrad_lds_launch(const float* x, const as_pcl* gin, const float* gz, 
   a.xgroups = (a.run + 7) / 8;
   const int lds_bytes = a.xgroups * 1024 + 16384;
   static AsPerDevice attr_set;
-  if (!attr_set.get()) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3d_wgrad_lds_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-    if (e != hipSuccess) { as_set_error("as_conv32_wgrad(3-D LDS): %s", hipGetErrorString(e)); return AS_ERR_LAUNCH; }
-    attr_set.set();
-  }
-  hipLaunchKernelGGL(conv3d_wgrad_lds_kernel, dim3(8 * ((a.nchunks + 7) / 8) * 3), dim3(256), lds_bytes, (hipStream_t)stream, a);
-  AS_CHECK_LAUNCH("as_conv32_wgrad(3-D LDS)");
-  return AS_OK;
+  void* kargs[] = {&a};
+  return as_launch_lds(reinterpret_cast<const void*>(conv3d_wgrad_lds_kernel), attr_set, 80 * 1024, lds_bytes,
+                       dim3(8 * ((a.nchunks + 7) / 8) * 3), dim3(256), kargs, "as_conv32_wgrad(3-D LDS)", (hipStream_t)stream);
 }

@@ -505,6 +505,15 @@ def conv32(x, gin: Pcl, packed_w, bias, gout: Pcl, shape: ConvShape, out=None, e
   return z
 
 
+def conv4(x4, g4: Pcl, packed_w, bias, gout: Pcl, shape: ConvShape, out=None, epilogue=0, scale=None, shift=None, stats=None):
+  """``conv32`` for a thin (PCL4) input: returns the PCL output buffer."""
+  z = out if out is not None else POOL.get(gout, x4.device)
+  sm, s2, sc = (stats.mean, stats.m2, stats.cnt) if stats is not None else (None, None, None)
+  call("as_conv4_fwd", ptr(x4), g4, ptr(packed_w), ptr(bias), ptr(z), gout, shape, int(epilogue), ptr(scale), ptr(shift),
+       LEAKY_SLOPE, ptr(sm), ptr(s2), ptr(sc), stream())
+  return z
+
+
 class StatParts(object):
   """BatchNorm partial moments written by a convolution epilogue: (count, mean, M2) per workgroup."""
 
@@ -1145,8 +1154,7 @@ class FeatureExtractorFn(torch.autograd.Function):
       if i == 0:
         wp = pack_special(wd, PACK_CONV4 + 3, 25, 25 * 128,
                           lambda w_, o_: call("as_conv4_pack_weights", ptr(w_), 3, ptr(o_), CONV5_S2, stream()))
-        call("as_conv4_fwd", ptr(in4), g4, ptr(wp), ptr(bd), ptr(out), gi, CONV5_S2, 0, None, None, LEAKY_SLOPE,
-             None, None, None, stream())
+        conv4(in4, g4, wp, bd, gi, CONV5_S2, out=out)
       else:
         conv32(levels[-1], geoms[-1], pack_weights(wd, CONV5_S2, False), bd, gi, CONV5_S2, out=out)
       geoms.append(gi); levels.append(out)
@@ -1379,9 +1387,7 @@ class EdgeRefineFn(torch.autograd.Function):
                        lambda w_, o_: call("as_conv4_pack_weights", ptr(w_), 4, ptr(o_), s33, stream()))
     if train:
       stats = StatParts(lib.as_conv4_stat_parts(g4, g, s33), dev)
-      z0 = POOL.get(g, dev)
-      call("as_conv4_fwd", ptr(in4), g4, ptr(wp4), ptr(b0), ptr(z0), g, s33, 0, None, None, LEAKY_SLOPE,
-           ptr(stats.mean), ptr(stats.m2), ptr(stats.cnt), stream())
+      z0 = conv4(in4, g4, wp4, b0, g, s33, stats=stats)
       st0 = bn_train_stats(stats, gamma0, beta0, rm0, rv0)
       fused_act = _FWD_ACT and need_bwd and all(lib.as_conv32_act_ok(g, g, conv_shape_2d(d)) == 1 for d in REFINE_DILATIONS)
       a0 = None if fused_act else bn_act(z0, st0, g)
@@ -1389,15 +1395,11 @@ class EdgeRefineFn(torch.autograd.Function):
       fused_act = False
       st0 = bn_eval_stats(gamma0, beta0, rm0, rv0)
       if need_bwd:
-        z0 = POOL.get(g, dev)
-        call("as_conv4_fwd", ptr(in4), g4, ptr(wp4), ptr(b0), ptr(z0), g, s33, 0, None, None, LEAKY_SLOPE, None, None,
-             None, stream())
+        z0 = conv4(in4, g4, wp4, b0, g, s33)
         a0 = bn_act(z0, st0, g)
       else:
         z0 = None
-        a0 = POOL.get(g, dev)
-        call("as_conv4_fwd", ptr(in4), g4, ptr(wp4), ptr(b0), ptr(a0), g, s33, 1, ptr(st0.scale), ptr(st0.shift),
-             LEAKY_SLOPE, None, None, None, stream())
+        a0 = conv4(in4, g4, wp4, b0, g, s33, epilogue=1, scale=st0.scale, shift=st0.shift)
     if not need_bwd and z0 is not None:
       POOL.put(z0, g); z0 = None
 
@@ -1516,16 +1518,13 @@ class EdgeRefineFn(torch.autograd.Function):
         # the nine shifted planes — no g_z0 write, no 32-channel re-read
         w_proj = pack_special(w0, PACK_MIRROR_TAP, 9, 288,                      # [9][32]: channel 0 of w0, taps mirrored
                               lambda w_, o_: call("as_mirror_taps_ch0", ptr(w_), 4, ptr(o_), None, stream()))
-        h_proj = _empty(B * 9 * H * W, dev)
-        call("as_conv4_wgrad_bnapply_proj", ptr(ctx.in4), g4, ptr(g_a), ptr(ctx.z0), g, s33, 4, ptr(st0.scale), ptr(st0.shift),
-             ptr(st0.mean), ptr(coef), LEAKY_SLOPE, ptr(w_proj), ptr(h_proj), ptr(sinks[0]), ptr(sinks[1]), 1, ptr(ws4),
-             stream())
-        g_z0 = None
+        h_proj, g_z0 = _empty(B * 9 * H * W, dev), None
+        entry, outs = "as_conv4_wgrad_bnapply_proj", (ptr(w_proj), ptr(h_proj))
       else:
-        h_proj = None
-        g_z0 = POOL.get(g, dev)
-        call("as_conv4_wgrad_bnapply", ptr(ctx.in4), g4, ptr(g_a), ptr(ctx.z0), g, s33, 4, ptr(st0.scale), ptr(st0.shift),
-             ptr(st0.mean), ptr(coef), LEAKY_SLOPE, ptr(g_z0), ptr(sinks[0]), ptr(sinks[1]), 1, ptr(ws4), stream())
+        h_proj, g_z0 = None, POOL.get(g, dev)
+        entry, outs = "as_conv4_wgrad_bnapply", (ptr(g_z0),)
+      call(entry, ptr(ctx.in4), g4, ptr(g_a), ptr(ctx.z0), g, s33, 4, ptr(st0.scale), ptr(st0.shift), ptr(st0.mean), ptr(coef),
+           LEAKY_SLOPE, *outs, ptr(sinks[0]), ptr(sinks[1]), 1, ptr(ws4), stream())
       dW0 = db0 = g_gamma0 = g_beta0 = None
     else:
       h_proj = None

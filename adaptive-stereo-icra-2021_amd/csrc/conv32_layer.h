@@ -86,8 +86,7 @@ LayerApplicable conv32_bwd_fused_applicable;
 int conv32_bwd_fused_slabs(void);      // workgroups of a launch = weight-gradient slabs = next-BatchNorm partials
 LayerBwdLaunch conv32_bwd_fused_launch;
 
-// conv32_mfma.hip: geometry checks every convolution entry point starts with
-int check_conv(const as_pcl* gin, const as_pcl* gout, const as_conv_shape* s, const char* who);
+#include "conv_entry.h"     // check_conv: the geometry checks every convolution entry point starts with
 
 // Diagnostic timing builds (EXTRA=-DWN_TIMING_BUILD / -DFB_TIMING_BUILD / -DBW_TIMING_BUILD): the kernels' per-wave cycle
 // counters live in one device buffer per launcher, zeroed before every launch ...

@@ -25,7 +25,6 @@
 // Measured (4 pairs, 375x1242): 116-121 TFLOP/s forward, 106-114 with the skip connection.
 #include "as_common.h"
 #include "conv_epilogue.h"
-#include "conv32_lds.h"
 
 #define TL_W 144                       // staged voxels per row: 8 + 128 + 8
 #define TL_ROW_BYTES (TL_W * 128)
@@ -383,19 +382,11 @@ int conv32_lds_grid(const as_pcl* gout) {
   return g;
 }
 
-int conv32_lds_launch(const float* x, const as_pcl* gin, const float* packed_w, const float* bias,
-                      float* z, const as_pcl* gout, const as_conv_shape* s,
-                      int epilogue, const float* ep_scale, const float* ep_shift, float slope,
-                      const float* residual, float* stat_mean, float* stat_m2, float* stat_cnt,
-                      const float* bn_z, const float* bn_scale, const float* bn_shift, const float* bn_mean,
-                      double* bn_partial, void* stream) {
+int conv32_lds_launch(const ConvFwdArgs& f, const as_pcl* gin, const as_pcl* gout, const as_conv_shape* s, const char* who,
+                      void* stream) {
   ConvLdsArgs a;
-  a.bn_z = bn_z; a.bn_scale = bn_scale; a.bn_shift = bn_shift; a.bn_mean = bn_mean; a.bn_partial = bn_partial;
-  a.x = x; a.wq = packed_w;
-  a.ep.bias = bias; a.ep.z = z; a.ep.ep_scale = ep_scale; a.ep.ep_shift = ep_shift; a.ep.residual = residual;
-  a.ep.stat_mean = epilogue == 0 ? stat_mean : nullptr; a.ep.stat_m2 = epilogue == 0 ? stat_m2 : nullptr;
-  a.ep.stat_cnt = epilogue == 0 ? stat_cnt : nullptr;
-  a.ep.epilogue = epilogue; a.ep.slope = slope;
+  a.bn_z = f.bn_z; a.bn_scale = f.bn_scale; a.bn_shift = f.bn_shift; a.bn_mean = f.bn_mean; a.bn_partial = f.bn_partial;
+  a.x = f.x; a.wq = f.w; a.ep = epilogue_args(f);
   a.gin = as_make_dev(gin); a.gout = as_make_dev(gout);
   a.dil = s->dil;
   a.tiles_per_row = (gout->W + 127) / 128;
@@ -404,12 +395,12 @@ int conv32_lds_launch(const float* x, const as_pcl* gin, const float* packed_w, 
   a.tiles_per_band = (a.ntiles + 7) / 8;
   a.wg_per_xcd = grid / 8;
   hipStream_t st = (hipStream_t)stream;
-  const int mode = bn_partial != nullptr ? 3 : (epilogue == 1 ? 1 : (a.ep.stat_mean != nullptr ? 0 : 2));
+  const int mode = f.bn_partial != nullptr ? 3 : (f.epilogue == 1 ? 1 : (a.ep.stat_mean != nullptr ? 0 : 2));
   const void* fn = nullptr;
 #define AS_LDS_PICK(M, R) (R ? reinterpret_cast<const void*>(conv32_lds_kernel<M, true>) : reinterpret_cast<const void*>(conv32_lds_kernel<M, false>))
-  const bool has_res = residual != nullptr;
+  const bool has_res = f.residual != nullptr;
   // eval forward of a BasicBlock: the residual is the input itself (same buffer, same padded geometry)
-  const bool res_self = mode == 1 && residual == x && gin->ph == gout->ph && gin->pw == gout->pw && gin->pd == gout->pd;
+  const bool res_self = mode == 1 && f.residual == f.x && gin->ph == gout->ph && gin->pw == gout->pw && gin->pd == gout->pd;
   fn = mode == 0 ? AS_LDS_PICK(0, has_res) : mode == 1 ? AS_LDS_PICK(1, has_res) : mode == 2 ? AS_LDS_PICK(2, has_res)
                                                                                               : AS_LDS_PICK(3, has_res);
   if (res_self) fn = reinterpret_cast<const void*>(conv32_lds_skip_kernel);
@@ -426,10 +417,10 @@ int conv32_lds_launch(const float* x, const as_pcl* gin, const float* packed_w, 
     hipMalloc(&trace_buf, trace_bytes); hipMemset(trace_buf, 0, trace_bytes); a.trace = trace_buf;
   }
 #endif
-  const int prof_id = mode == 3 ? 6 : 2;
+  const int prof_id = mode == 3 ? AS_PROF_CONV32_LDS_BNBWD : AS_PROF_CONV32_LDS;
   as_prof_mark(prof_id, st, 1, 0.0);
   void* kargs[] = {&a};
-  if (int e = as_launch_lds(fn, attr_set[fi], TL_LDS_BYTES, TL_LDS_BYTES, dim3(grid), dim3(256), kargs, "as_conv32_fwd(lds)", st)) return e;
+  if (int e = as_launch_lds(fn, attr_set[fi], TL_LDS_BYTES, TL_LDS_BYTES, dim3(grid), dim3(256), kargs, who, st)) return e;
 #ifdef AS_LDS_TRACE_BUILD
   if (a.trace) {
     hipStreamSynchronize(st);
@@ -438,7 +429,7 @@ int conv32_lds_launch(const float* x, const as_pcl* gin, const float* packed_w, 
   }
 #endif
   as_prof_mark(prof_id, st, 0, 2.0 * (double)gout->B * gout->H * gout->W * 1024.0 * 9);
-  AS_CHECK_LAUNCH("as_conv32_fwd(lds)");
+  AS_CHECK_LAUNCH(who);
   return AS_OK;
 }
 
@@ -756,12 +747,12 @@ int conv32_wgrad_lds_slabs(const as_pcl* gout) {
 
 bool conv32_wgrad_bnapply_ok(const as_pcl* gout) { return wgrad_lds2(gout); }
 
-int conv32_wgrad_lds_launch(const float* x, const as_pcl* gin, const float* gz, const as_pcl* gout,
-                            const as_conv_shape* s, float* partial, float* partial_db, const WgradBnApply* bn,
-                            void* stream) {
+int conv32_wgrad_lds_launch(const ConvWgradArgs& w, const as_pcl* gin, const as_pcl* gout, const as_conv_shape* s,
+                            const char* who, void* stream) {
   static AsPerDevice attr_set[3];                          // per kernel, each at its first launch
+  const WgradBnApply* bn = w.bn;
   WgradLdsArgs a;
-  a.x = x; a.gz = gz; a.partial = partial; a.partial_db = partial_db;
+  a.x = w.x; a.gz = w.gz; a.partial = w.partial; a.partial_db = w.partial_db;
   a.gin = as_make_dev(gin); a.gout = as_make_dev(gout);
   a.dil = s->dil;
   a.tiles_per_row = (gout->W + 127) / 128;
@@ -771,7 +762,7 @@ int conv32_wgrad_lds_launch(const float* x, const as_pcl* gin, const float* gz, 
   a.wg_per_xcd = grid / 8;
   a.bn_z = nullptr; a.bn_scale = a.bn_shift = a.bn_mean = a.bn_coef = nullptr; a.gz_out = nullptr; a.slope = 0.f;
   if (bn != nullptr) {
-    if (!wgrad_lds2(gout)) { as_set_error("as_conv32_wgrad_bnapply: configuration not supported"); return AS_ERR_ARG; }
+    if (!wgrad_lds2(gout)) { as_set_error("%s: configuration not supported", who); return AS_ERR_ARG; }
     a.bn_z = bn->z; a.bn_scale = bn->scale; a.bn_shift = bn->shift; a.bn_mean = bn->mean; a.bn_coef = bn->coef;
     a.gz_out = bn->gz_out; a.slope = bn->slope;
   }
@@ -782,6 +773,6 @@ int conv32_wgrad_lds_launch(const float* x, const as_pcl* gin, const float* gz, 
                              reinterpret_cast<const void*>(conv32_wgrad_lds2_kernel<true>)};
   const int lds[3] = {TLW_LDS_BYTES, TLW2_LDS_BYTES, TLW2A_LDS_BYTES};
   void* kargs[] = {&a};
-  return as_launch_lds(fn[ki], attr_set[ki], lds[ki], lds[ki], dim3(grid), dim3(ki ? 512 : 256), kargs, "as_conv32_wgrad(lds)",
+  return as_launch_lds(fn[ki], attr_set[ki], lds[ki], lds[ki], dim3(grid), dim3(ki ? 512 : 256), kargs, who,
                        (hipStream_t)stream);
 }

@@ -26,22 +26,8 @@
 // The weight gradient is a second kernel: M = ci, N = co, K = voxels.
 #include "as_common.h"
 #include "conv_epilogue.h"
-#include "conv32_lds.h"
 #include <cstdlib>
 #include "conv3d_lds.h"
-#include "conv32_layer.h"
-#include "conv32_s2.h"
-
-static bool wgrad_lds_applicable(const as_pcl* gin, const as_pcl* gout, const as_conv_shape* s);
-
-// The 5x5 stride-2 layers of the feature head on csrc/conv32_s2.hip (1, default) or on the generic direct-load kernels (0):
-// same bits either way (the parity tests compare them); returns the previous setting.
-static int g_conv32_s2 = 1;
-extern "C" int as_conv32_s2_enable(int on) {
-  const int prev = g_conv32_s2;
-  if (on == 0 || on == 1) g_conv32_s2 = on;
-  return prev;
-}
 
 struct ConvArgs {
   const float* x;
@@ -100,7 +86,7 @@ __device__ __forceinline__ void conv32_fwd_body(const ConvArgs& p, const int blo
 
   // the bias is requested first and needed (accumulator init) only after the prologue; the load is unconditional
   // so that no select forces a wait here
-  const float bias_v = p.ep.bias[li];                      // never null here: launch_conv32 substitutes 32 zeros
+  const float bias_v = p.ep.bias[li];                      // never null here: the launchers substitute 32 zeros
   __builtin_amdgcn_sched_barrier(0);
 
   // Operands are requested PF taps ahead (a ring of PF+1 register sets): on the small maps (24x78 at 1/16 resolution)
@@ -168,7 +154,7 @@ __global__ __launch_bounds__(256) void conv32_dgrad_s2_kernel(DgradS2Args p) {
 #ifndef CONV32_SPLITK_MAX_M
 #define CONV32_SPLITK_MAX_M 32768
 #endif
-static inline bool conv32_splitk_applies(int ntaps, long M) {
+bool conv32_splitk_applies(int ntaps, int64_t M) {
   // 25 taps (the strided head's 5x5 convolutions, round 3): a one-wave chain is 400 dependent MFMAs = 12 us; on the two
   // smallest levels (<= 16 K output voxels: fewer wave tiles than the chip has SIMDs) the split chain of 112 wins
   return (ntaps == 9 && M <= CONV32_SPLITK_MAX_M) || (ntaps == 25 && M <= CONV32_SPLITK_MAX_M / 2);
@@ -492,17 +478,10 @@ struct PendingReduce { const float* partial; const float* partial_db; int nchunk
 static std::mutex g_defer_mutex;
 static bool g_defer_on = false;
 static std::vector<PendingReduce> g_defer_jobs;
-static void wgrad_reduce(hipStream_t st, const float* partial, const float* partial_db, int nchunks, int T, float* dW, float* db,
-                         int accumulate);
-// (for the other translation units: trunk.hip)
+
+// every 32->32 weight-gradient entry point ends in this (conv_entry.hip, conv32_layer.hip, trunk.hip)
 void as_wgrad_reduce_enqueue(hipStream_t st, const float* partial, const float* partial_db, int nchunks, int T, float* dW,
                              float* db, int accumulate) {
-  wgrad_reduce(st, partial, partial_db, nchunks, T, dW, db, accumulate);
-}
-
-// every weight-gradient entry point ends in this
-static void wgrad_reduce(hipStream_t st, const float* partial, const float* partial_db, int nchunks, int T, float* dW, float* db,
-                         int accumulate) {
   {
     std::lock_guard<std::mutex> lock(g_defer_mutex);
     // only reductions that ACCUMULATE into a gradient sink wait for the flush; a dW that is handed back to the caller
@@ -561,8 +540,8 @@ extern "C" int as_wgrad_defer_flush(void* stream) {
 }
 
 // ---------------------------------------------------------------------------------
-// Host side
-static int fill_taps(const as_pcl* gin, const as_conv_shape* s, int* tap_off, const char* who) {
+// Host side: one launcher per kernel family (the entry points, their checks and route decisions: conv_entry.hip)
+int fill_taps(const as_pcl* gin, const as_conv_shape* s, int* tap_off, const char* who) {
   const int T = s->kd * s->kh * s->kw;
   AS_CHECK_ARG(T >= 1 && T <= AS_MAX_TAPS, "%s: %d taps unsupported", who, T);
   AS_CHECK_ARG(s->dil >= 1 && s->stride >= 1, "%s: bad dilation/stride", who);
@@ -579,28 +558,7 @@ static int fill_taps(const as_pcl* gin, const as_conv_shape* s, int* tap_off, co
   return AS_OK;
 }
 
-int check_conv(const as_pcl* gin, const as_pcl* gout, const as_conv_shape* s, const char* who) {
-  AS_CHECK_ARG(as_pcl_ok(gin) && as_pcl_ok(gout) && s, "%s: bad geometry", who);
-  AS_CHECK_ARG(gin->B == gout->B && gin->D == gout->D, "%s: batch/depth mismatch", who);
-  // output extent of the convolution
-  const int eh = (gin->H + 2 * s->pad_h - s->dil * (s->kh - 1) - 1) / s->stride + 1;
-  const int ew = (gin->W + 2 * s->pad_w - s->dil * (s->kw - 1) - 1) / s->stride + 1;
-  AS_CHECK_ARG(eh == gout->H && ew == gout->W, "%s: output extent %dx%d != conv result %dx%d", who,
-               gout->H, gout->W, eh, ew);
-  if (s->kd > 1)
-    AS_CHECK_ARG(gin->D + 2 * s->pad_d - s->dil * (s->kd - 1) == gout->D, "%s: depth extent mismatch", who);
-  // every tap of every output must land inside the input's halo
-  const int reach_h_lo = s->pad_h, reach_w_lo = s->pad_w;
-  const int reach_h_hi = (gout->H - 1) * s->stride + s->dil * (s->kh - 1) - s->pad_h - (gin->H - 1);
-  const int reach_w_hi = (gout->W - 1) * s->stride + s->dil * (s->kw - 1) - s->pad_w - (gin->W - 1);
-  AS_CHECK_ARG(reach_h_lo <= gin->ph && reach_w_lo <= gin->pw && reach_h_hi <= gin->ph && reach_w_hi <= gin->pw,
-               "%s: input halo (%d,%d) too small for padding", who, gin->ph, gin->pw);
-  if (s->kd > 1) AS_CHECK_ARG(s->pad_d <= gin->pd && s->dil * (s->kd - 1) - s->pad_d <= gin->pd,
-                              "%s: input depth halo too small", who);
-  return AS_OK;
-}
-
-__device__ float g_zero_bias[32];          // zero-initialised: the bias of a convolution that has none
+__device__ float g_zero_bias[32];         // zero-initialised: the bias of a convolution that has none
 
 // 32 zeros in device memory (the convolution bodies read their bias unconditionally), per HIP device
 static const float* zero_bias_ptr(void) {
@@ -614,15 +572,22 @@ static const float* zero_bias_ptr(void) {
   return zeros[d];
 }
 
-static int launch_conv32(const ConvArgs& args, hipStream_t st, const char* who) {
-  ConvArgs a = args;
+int conv32_generic_launch(const ConvFwdArgs& f, const as_pcl* gin, const as_pcl* gout, const as_conv_shape* s, bool splitk,
+                          const char* who, void* stream) {
+  ConvArgs a;
+  a.x = f.x; a.wp = f.w; a.ep = epilogue_args(f);
+  a.gin = as_make_dev(gin); a.gout = as_make_dev(gout);
+  a.M = (int)((int64_t)gout->B * gout->D * gout->H * gout->W); a.ntaps = s->kd * s->kh * s->kw;
+  a.map.Hl = gout->H; a.map.Wl = gout->W; a.map.in_stride = s->stride; a.map.out_stride = 1; a.map.out_oy = 0; a.map.out_ox = 0;
+  if (int e = fill_taps(gin, s, a.tap_off, who)) return e;
   if (a.ep.bias == nullptr) {
     const float* zeros = zero_bias_ptr();
     if (zeros == nullptr) { as_set_error("%s: no address for the zero bias", who); return AS_ERR_LAUNCH; }
     a.ep.bias = zeros;
   }
+  hipStream_t st = (hipStream_t)stream;
   const dim3 grid(as_div_up(a.M, 128)), block(256);
-  if (conv32_splitk_applies(a.ntaps, a.M)) {
+  if (splitk) {
     if (a.ntaps == 9) hipLaunchKernelGGL(conv32_fwd_splitk_kernel<9>, dim3(as_div_up(a.M, 32)), block, 0, st, a);
     else hipLaunchKernelGGL(conv32_fwd_splitk_kernel<25>, dim3(as_div_up(a.M, 32)), block, 0, st, a);
     return AS_OK;
@@ -671,40 +636,14 @@ extern "C" int as_conv32_dgrad_s2_pack(const float* w, float* packed, void* stre
   return AS_OK;
 }
 
-extern "C" int as_conv32_dgrad_s2(const float* gz, const as_pcl* ggz, const float* w, float* gx, const as_pcl* ggx,
-                                  float* workspace, void* stream) {
-  AS_CHECK_ARG(w && workspace, "as_conv32_dgrad_s2: null pointer");
-  if (int e = as_conv32_dgrad_s2_pack(w, workspace, stream)) return e;
-  return as_conv32_dgrad_s2_packed(gz, ggz, workspace, gx, ggx, stream);
-}
-
-// Whether as_conv32_dgrad_s2_packed launches conv32_s2_dgrad_kernel (the entry point's own test, switch included).
-static bool conv32_s2_dgrad_takes(const as_pcl* ggz, const as_pcl* ggx) {
-  return g_conv32_s2 && conv32_s2_dgrad_applicable(ggz, ggx);
-}
-extern "C" int as_conv32_s2_dgrad_ok(const as_pcl* ggz, const as_pcl* ggx) {
-  if (!as_pcl_ok(ggz) || !as_pcl_ok(ggx)) return AS_ERR_ARG;
-  return conv32_s2_dgrad_takes(ggz, ggx) ? 1 : 0;
-}
-
-extern "C" int as_conv32_dgrad_s2_packed(const float* gz, const as_pcl* ggz, const float* packed, float* gx, const as_pcl* ggx,
-                                         void* stream) {
-  const float* w = packed; float* workspace = const_cast<float*>(packed);
-  AS_CHECK_ARG(as_pcl_ok(ggz) && as_pcl_ok(ggx) && gz && w && gx && workspace, "as_conv32_dgrad_s2: bad argument");
-  AS_CHECK_ARG(ggz->D == 1 && ggx->D == 1 && ggz->B == ggx->B, "as_conv32_dgrad_s2: 2-D tensors of equal batch expected");
-  AS_CHECK_ARG(ggz->H == (ggx->H - 1) / 2 + 1 && ggz->W == (ggx->W - 1) / 2 + 1,
-               "as_conv32_dgrad_s2: gz extent is not that of a 5x5 stride-2 pad-2 convolution of gx's extent");
-  AS_CHECK_ARG(ggz->ph >= 1 && ggz->pw >= 1, "as_conv32_dgrad_s2: gz needs a zero halo of 1");
-  hipStream_t st = (hipStream_t)stream;
-  if (conv32_s2_dgrad_takes(ggz, ggx)) {
-    as_prof_mark(AS_PROF_CONV32, st, 1, 0.0);
-    if (int e = conv32_s2_dgrad_launch(gz, ggz, packed, gx, ggx, stream)) return e;
-    as_prof_mark(AS_PROF_CONV32, st, 0, 2.0 * (double)ggx->B * ggz->H * ggz->W * 1024.0 * 25.0);
-    AS_CHECK_LAUNCH("as_conv32_dgrad_s2(staged)");
-    return AS_OK;
-  }
+// The four phases on the direct-load body in one launch (maps too small for the staged rows of conv32_s2.hip)
+int conv32_dgrad_s2_generic_launch(const float* gz, const as_pcl* ggz, const float* packed, float* gx, const as_pcl* ggx,
+                                   const char* who, void* stream) {
+  const float* zero_bias = zero_bias_ptr();                // (the bias of conv32_fwd_body is read unconditionally)
+  if (zero_bias == nullptr) { as_set_error("%s: no address for the zero bias", who); return AS_ERR_LAUNCH; }
+  const ConvFwdArgs f = {gz, packed, zero_bias, gx};
   const int Wp = ggz->W + 2 * ggz->pw;
-  const float* wp = workspace;
+  const float* wp = packed;
   DgradS2Args args;
   int total = 0, ph = 0;
   for (int py = 0; py < 2; ++py)
@@ -718,9 +657,7 @@ extern "C" int as_conv32_dgrad_s2_packed(const float* gz, const as_pcl* ggz, con
           a.tap_off[n] = ((py + 2 - j) / 2) * Wp + (px + 2 - l) / 2;
           ++n;
         }
-      a.x = gz; a.wp = wp;
-      a.ep.bias = nullptr; a.ep.z = gx; a.ep.ep_scale = nullptr; a.ep.ep_shift = nullptr; a.ep.residual = nullptr;
-      a.ep.stat_mean = nullptr; a.ep.stat_m2 = nullptr; a.ep.stat_cnt = nullptr; a.ep.epilogue = 0; a.ep.slope = 0.f;
+      a.x = f.x; a.wp = wp; a.ep = epilogue_args(f);
       a.gin = as_make_dev(ggz); a.gout = as_make_dev(ggx);
       a.map.Hl = Hl > 0 ? Hl : 1; a.map.Wl = Wl > 0 ? Wl : 1; a.map.in_stride = 1; a.map.out_stride = 2; a.map.out_oy = py; a.map.out_ox = px;
       a.M = (Hl > 0 && Wl > 0) ? ggx->B * Hl * Wl : 0; a.ntaps = n;
@@ -728,13 +665,7 @@ extern "C" int as_conv32_dgrad_s2_packed(const float* gz, const as_pcl* ggz, con
       total += args.nblk[ph];
       wp += n * 1024;
     }
-  const float* zero_bias = zero_bias_ptr();                // (the bias of conv32_fwd_body is read unconditionally)
-  if (zero_bias == nullptr) { as_set_error("as_conv32_dgrad_s2: no address for the zero bias"); return AS_ERR_LAUNCH; }
-  for (int i = 0; i < 4; ++i) args.ph[i].ep.bias = zero_bias;
-  as_prof_mark(AS_PROF_CONV32, st, 1, 0.0);
-  if (total > 0) hipLaunchKernelGGL(conv32_dgrad_s2_kernel, dim3(total), dim3(256), 0, st, args);
-  as_prof_mark(AS_PROF_CONV32, st, 0, 2.0 * (double)ggx->B * ggz->H * ggz->W * 1024.0 * 25.0);
-  AS_CHECK_LAUNCH("as_conv32_dgrad_s2");
+  if (total > 0) hipLaunchKernelGGL(conv32_dgrad_s2_kernel, dim3(total), dim3(256), 0, (hipStream_t)stream, args);
   return AS_OK;
 }
 
@@ -832,33 +763,6 @@ extern "C" int as_conv32_wino_pack_weights(const float* w, float* packed, int tr
   return AS_OK;
 }
 
-// Weight gradient fused with stage 3 of the layer's BatchNorm backward (the gradient operand arrives as g_a).
-extern "C" int as_conv32_wgrad_bnapply_ok(const as_pcl* gin, const as_pcl* gout, const as_conv_shape* s) {
-  if (!as_pcl_ok(gin) || !as_pcl_ok(gout) || !s) return AS_ERR_ARG;
-  return wgrad_lds_applicable(gin, gout, s) && conv32_wgrad_bnapply_ok(gout) ? 1 : 0;
-}
-
-extern "C" int as_conv32_wgrad_bnapply(const float* x, const as_pcl* gin, const float* g_a, const float* z,
-                                       const as_pcl* gout, const as_conv_shape* s, const float* scale,
-                                       const float* shift, const float* mean, const float* coef, float slope,
-                                       float* g_z, float* dW, float* db, int accumulate, float* workspace, void* stream) {
-  if (int e = check_conv(gin, gout, s, "as_conv32_wgrad_bnapply")) return e;
-  AS_CHECK_ARG(x && g_a && z && scale && shift && mean && coef && g_z && dW && workspace, "as_conv32_wgrad_bnapply: null pointer");
-  AS_CHECK_ARG(wgrad_lds_applicable(gin, gout, s) && conv32_wgrad_bnapply_ok(gout),
-               "as_conv32_wgrad_bnapply: configuration not supported (as_conv32_wgrad_bnapply_ok() == 0)");
-  const int T = 9;
-  const int slabs = conv32_wgrad_lds_slabs(gout);
-  float* partial_db = workspace + (int64_t)slabs * T * 1024;
-  WgradBnApply bn = {z, scale, shift, mean, coef, g_z, slope};
-  hipStream_t st = (hipStream_t)stream;
-  as_prof_mark(3, st, 1, 0.0);
-  if (int e = conv32_wgrad_lds_launch(x, gin, g_a, gout, s, workspace, partial_db, &bn, stream)) return e;
-  as_prof_mark(3, st, 0, 2.0 * (double)gout->B * gout->D * gout->H * gout->W * 1024.0 * T);
-  wgrad_reduce(st, workspace, partial_db, slabs, T, dW, db, accumulate);
-  AS_CHECK_LAUNCH("as_conv32_wgrad_bnapply(reduce)");
-  return AS_OK;
-}
-
 // Host-side view of conv3d_wgrad_lds_kernel's work assignment (csrc/conv3d_lds.h: conv3d_wgrad_assign — the very function the
 // kernel calls): for workgroup `block` of a launch over `ntiles` tiles in `nchunks` chunks, its chunk, kd and extra tile (-1:
 // none).  Returns 1 for a working block, 0 for a padding block.  No GPU involved: the CPU suite walks it.
@@ -868,101 +772,13 @@ extern "C" int as_conv3d_wgrad_lds_assignment(int ntiles, int nchunks, int block
   return conv3d_wgrad_assign(block, ntiles, nchunks, chunk, kd, extra_tile) ? 1 : 0;
 }
 
-// Convolution (data gradient) fused with stage 1 of the BatchNorm backward that consumes its output.
-extern "C" int as_conv32_bnbwd_parts(const as_pcl* gin, const as_pcl* gout, const as_conv_shape* s) {
-  if (!as_pcl_ok(gin) || !as_pcl_ok(gout) || !s) return AS_ERR_ARG;
-  return conv32_lds_applicable(gin, gout, s) ? conv32_lds_grid(gout) : 0;
-}
-
-extern "C" int as_conv32_fwd_bnbwd(const float* x, const as_pcl* gin, const float* packed_w, float* z, const as_pcl* gout,
-                                   const as_conv_shape* s, const float* residual, const float* bn_z,
-                                   const float* bn_scale, const float* bn_shift, const float* bn_mean, float slope,
-                                   float* bn_workspace, void* stream) {
-  if (int e = check_conv(gin, gout, s, "as_conv32_fwd_bnbwd")) return e;
-  AS_CHECK_ARG(x && packed_w && z && bn_z && bn_scale && bn_shift && bn_mean && bn_workspace, "as_conv32_fwd_bnbwd: null pointer");
-  AS_CHECK_ARG(conv32_lds_applicable(gin, gout, s), "as_conv32_fwd_bnbwd: configuration not supported (as_conv32_bnbwd_parts() == 0)");
-  AS_CHECK_ARG(((uintptr_t)bn_workspace & 7) == 0, "as_conv32_fwd_bnbwd: workspace must be 8-byte aligned");
-  return conv32_lds_launch(x, gin, packed_w, nullptr, z, gout, s, 0, nullptr, nullptr, slope, residual, nullptr, nullptr,
-                           nullptr, bn_z, bn_scale, bn_shift, bn_mean, reinterpret_cast<double*>(bn_workspace), stream);
-}
-
-extern "C" int as_conv32_num_blocks(const as_pcl* gout) {
-  if (!as_pcl_ok(gout)) return AS_ERR_ARG;
-  const int64_t M = (int64_t)gout->B * gout->D * gout->H * gout->W;
-  return as_div_up(M, 128);
-}
-
-// Number of BatchNorm partials as_conv32_fwd writes for this configuration.
-extern "C" int as_conv32_stat_parts(const as_pcl* gin, const as_pcl* gout, const as_conv_shape* s) {
-  if (!as_pcl_ok(gin) || !as_pcl_ok(gout) || !s) return AS_ERR_ARG;
-  if (conv32_lds_applicable(gin, gout, s)) return conv32_lds_grid(gout);
-  if (conv3d_lds_applicable(gin, gout, s)) return conv3d_lds_grid(gout);
-  const int64_t M = (int64_t)gout->B * gout->D * gout->H * gout->W;
-  if (conv32_splitk_applies(s->kd * s->kh * s->kw, M)) return as_div_up(M, 32);     // one partial per 32-voxel tile
-  return as_conv32_num_blocks(gout);
-}
-
-// Whether as_conv32_fwd launches conv32_s2_fwd_kernel (the entry point's own test, switch included; as_conv32_s2_fwd_ok
-// answers it for epilogue 0 without residual and moments): no LDS kernel takes the layer, and split-K has precedence.
-static bool conv32_s2_fwd_takes(const as_pcl* gin, const as_pcl* gout, const as_conv_shape* s, int epilogue, bool residual,
-                                bool moments) {
-  if (conv32_lds_applicable(gin, gout, s) || conv3d_lds_applicable(gin, gout, s)) return false;
-  const int64_t M_all = (int64_t)gout->B * gout->D * gout->H * gout->W;
-  return epilogue == 0 && !residual && !moments && g_conv32_s2 && conv32_s2_fwd_applicable(gin, gout, s) &&
-         !conv32_splitk_applies(25, M_all);
-}
-extern "C" int as_conv32_s2_fwd_ok(const as_pcl* gin, const as_pcl* gout, const as_conv_shape* s) {
-  if (check_conv(gin, gout, s, "as_conv32_s2_fwd_ok")) return AS_ERR_ARG;
-  return conv32_s2_fwd_takes(gin, gout, s, 0, false, false) ? 1 : 0;
-}
-
-extern "C" int as_conv32_fwd(const float* x, const as_pcl* gin, const float* packed_w, const float* bias,
-                             float* z, const as_pcl* gout, const as_conv_shape* s,
-                             int epilogue, const float* ep_scale, const float* ep_shift, float slope,
-                             const float* residual, float* stat_mean, float* stat_m2, float* stat_cnt, void* stream) {
-  if (int e = check_conv(gin, gout, s, "as_conv32_fwd")) return e;
-  AS_CHECK_ARG(x && packed_w && z, "as_conv32_fwd: null pointer");
-  AS_CHECK_ARG(epilogue_args_ok(epilogue, ep_scale, ep_shift, stat_mean, stat_m2, stat_cnt), "as_conv32_fwd: bad epilogue arguments");
-  if (conv32_lds_applicable(gin, gout, s))
-    return conv32_lds_launch(x, gin, packed_w, bias, z, gout, s, epilogue, ep_scale, ep_shift, slope, residual,
-                             stat_mean, stat_m2, stat_cnt, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
-  if (conv3d_lds_applicable(gin, gout, s))
-    return conv3d_lds_launch(x, gin, packed_w, bias, z, gout, epilogue, ep_scale, ep_shift, slope, residual,
-                             stat_mean, stat_m2, stat_cnt, stream);
-  const int64_t M_all = (int64_t)gout->B * gout->D * gout->H * gout->W;
-  if (conv32_s2_fwd_takes(gin, gout, s, epilogue, residual != nullptr, stat_mean != nullptr)) {
-    // the strided head of the feature towers on maps that fill the chip: coalesced row staging (csrc/conv32_s2.hip)
-    hipStream_t st2 = (hipStream_t)stream;
-    as_prof_mark(0, st2, 1, 0.0);
-    if (int e = conv32_s2_fwd_launch(x, gin, packed_w, bias, z, gout, stream)) return e;
-    as_prof_mark(0, st2, 0, 2.0 * (double)M_all * 1024.0 * 25.0);
-    AS_CHECK_LAUNCH("as_conv32_fwd(5x5 stride 2)");
-    return AS_OK;
-  }
-  ConvArgs a;
-  a.x = x; a.wp = packed_w;
-  a.ep.bias = bias; a.ep.z = z; a.ep.ep_scale = ep_scale; a.ep.ep_shift = ep_shift; a.ep.residual = residual;
-  a.ep.stat_mean = epilogue == 0 ? stat_mean : nullptr; a.ep.stat_m2 = epilogue == 0 ? stat_m2 : nullptr;
-  a.ep.stat_cnt = epilogue == 0 ? stat_cnt : nullptr;
-  a.ep.epilogue = epilogue; a.ep.slope = slope;
-  a.gin = as_make_dev(gin); a.gout = as_make_dev(gout);
-  const int64_t M = (int64_t)gout->B * gout->D * gout->H * gout->W;
-  a.M = (int)M; a.ntaps = s->kd * s->kh * s->kw;
-  a.map.Hl = gout->H; a.map.Wl = gout->W; a.map.in_stride = s->stride; a.map.out_stride = 1; a.map.out_oy = 0; a.map.out_ox = 0;
-  if (int e = fill_taps(gin, s, a.tap_off, "as_conv32_fwd")) return e;
-  as_prof_mark(0, (hipStream_t)stream, 1, 0.0);
-  hipStream_t st = (hipStream_t)stream;
-  if (int e = launch_conv32(a, st, "as_conv32_fwd")) return e;
-  as_prof_mark(0, (hipStream_t)stream, 0, 2.0 * (double)M * 1024.0 * a.ntaps);
-  AS_CHECK_LAUNCH("as_conv32_fwd");
-  return AS_OK;
-}
-
-// Rows are cut into segments only while whole rows would leave SIMDs idle (rows x tap groups < 1024 waves): every
-// extra segment is an extra partial slab to write and reduce.
-static int wgrad_segments(const as_pcl* gout, const as_conv_shape* s, int* seg_steps) {
-  const int T = s->kd * s->kh * s->kw;
-  const int groups = T / ((T % 3 == 0) ? 3 : (T % 5 == 0 ? 5 : 1));
+// Plan of conv32_wgrad_kernel for a layer.  Rows are cut into segments only while whole rows would leave SIMDs idle (rows x
+// tap groups < 1024 waves): every extra segment is an extra partial slab to write and reduce.
+Wgrad32Plan conv32_wgrad_plan(const as_pcl* gout, const as_conv_shape* s) {
+  Wgrad32Plan p;
+  p.T = s->kd * s->kh * s->kw;
+  p.tap_group = (p.T % 3 == 0) ? 3 : (p.T % 5 == 0 ? 5 : 1);
+  const int groups = p.T / p.tap_group;
   const int nsteps = (gout->W + 1) >> 1;
   const long waves = (long)gout->B * gout->D * gout->H * groups;
   int nseg = 1;
@@ -973,46 +789,17 @@ static int wgrad_segments(const as_pcl* gout, const as_conv_shape* s, int* seg_s
     if (nseg < 1) nseg = 1;
   }
   int steps = (nsteps + nseg - 1) / nseg;
-  steps = (steps + 7) / 8 * 8;
-  *seg_steps = steps;
-  return (nsteps + steps - 1) / steps;
-}
-static int wgrad_plan(const as_pcl* gout, const as_conv_shape* s, int* tg, int* rows_per_chunk, int* nchunks) {
-  const int T = s->kd * s->kh * s->kw;
-  *tg = (T % 3 == 0) ? 3 : (T % 5 == 0 ? 5 : 1);
-  int seg_steps;
-  const int rows = gout->B * gout->D * gout->H * wgrad_segments(gout, s, &seg_steps);       // work units (row segments)
+  p.seg_steps = (steps + 7) / 8 * 8;
+  p.nseg = (nsteps + p.seg_steps - 1) / p.seg_steps;
+  const int rows = gout->B * gout->D * gout->H * p.nseg;                  // work units (row segments)
   // aim at ~4 waves per SIMD over the chip (256 CUs x 4 SIMDs), at least 4 units (one per
   // wave) per chunk, and cap the slab count so the partial buffer stays a few MB.
-  const int groups = T / *tg;
   int want_chunks = (4096 + groups * 4 - 1) / (groups * 4);
   if (want_chunks > 512) want_chunks = 512;
-  int rpc = (rows + want_chunks - 1) / want_chunks;
-  if (rpc < 4) rpc = 4;
-  *rows_per_chunk = rpc;
-  *nchunks = (rows + rpc - 1) / rpc;
-  return T;
-}
-
-static bool wgrad_lds_applicable(const as_pcl* gin, const as_pcl* gout, const as_conv_shape* s) {
-  return conv32_lds_applicable(gin, gout, s) && gout->pw >= 8;   // G groups beyond W read 8 zero halo voxels
-}
-
-// Segments per row of conv32_wgrad_kernel for this layer; 0 when an LDS kernel takes it (as as_conv32_wgrad decides).
-extern "C" int as_conv32_wgrad_segments(const as_pcl* gin, const as_pcl* gout, const as_conv_shape* s) {
-  if (check_conv(gin, gout, s, "as_conv32_wgrad_segments")) return AS_ERR_ARG;
-  if (wgrad_lds_applicable(gin, gout, s) || conv3d_wgrad_lds_applicable(gin, gout, s)) return 0;
-  int seg_steps;
-  return wgrad_segments(gout, s, &seg_steps);
-}
-
-extern "C" int64_t as_conv32_wgrad_workspace(const as_pcl* gin, const as_pcl* gout, const as_conv_shape* s) {
-  if (!as_pcl_ok(gin) || !as_pcl_ok(gout) || !s) return -1;
-  int tg, rpc, nchunks;
-  const int T = wgrad_plan(gout, s, &tg, &rpc, &nchunks);
-  if (wgrad_lds_applicable(gin, gout, s)) nchunks = conv32_wgrad_lds_slabs(gout);
-  if (conv3d_wgrad_lds_applicable(gin, gout, s)) nchunks = conv3d_wgrad_lds_slabs(gout);
-  return (int64_t)nchunks * T * 1024 + (int64_t)nchunks * 32;
+  p.rows_per_chunk = (rows + want_chunks - 1) / want_chunks;
+  if (p.rows_per_chunk < 4) p.rows_per_chunk = 4;
+  p.nchunks = (rows + p.rows_per_chunk - 1) / p.rows_per_chunk;
+  return p;
 }
 
 template <int TG>
@@ -1022,49 +809,18 @@ static void launch_wgrad(const WgradArgs& a, int groups, int nchunks, hipStream_
   hipLaunchKernelGGL(conv32_wgrad_kernel<TG>, dim3(8 * per_xcd * groups), dim3(256), lds, st, a);
 }
 
-extern "C" int as_conv32_wgrad(const float* x, const as_pcl* gin, const float* gz, const as_pcl* gout,
-                               const as_conv_shape* s, float* dW, float* db, int accumulate, float* workspace,
-                               void* stream) {
-  if (int e = check_conv(gin, gout, s, "as_conv32_wgrad")) return e;
-  AS_CHECK_ARG(x && gz && dW && workspace, "as_conv32_wgrad: null pointer");
-  int tg, rpc, nchunks;
-  const int T = wgrad_plan(gout, s, &tg, &rpc, &nchunks);
-  if (wgrad_lds_applicable(gin, gout, s)) {
-    const int slabs = conv32_wgrad_lds_slabs(gout);
-    float* partial_db = workspace + (int64_t)slabs * T * 1024;
-    hipStream_t st = (hipStream_t)stream;
-    as_prof_mark(3, st, 1, 0.0);
-    if (int e = conv32_wgrad_lds_launch(x, gin, gz, gout, s, workspace, partial_db, nullptr, stream)) return e;
-    as_prof_mark(3, st, 0, 2.0 * (double)gout->B * gout->D * gout->H * gout->W * 1024.0 * T);
-    wgrad_reduce(st, workspace, partial_db, slabs, T, dW, db, accumulate);
-    AS_CHECK_LAUNCH("as_conv32_wgrad(reduce)");
-    return AS_OK;
-  }
-  if (conv3d_wgrad_lds_applicable(gin, gout, s)) {
-    const int slabs = conv3d_wgrad_lds_slabs(gout);
-    float* partial_db = workspace + (int64_t)slabs * T * 1024;
-    hipStream_t st = (hipStream_t)stream;
-    as_prof_mark(AS_PROF_WGRAD3D_LDS, st, 1, 0.0);
-    if (int e = conv3d_wgrad_lds_launch(x, gin, gz, gout, workspace, partial_db, stream)) return e;
-    as_prof_mark(AS_PROF_WGRAD3D_LDS, st, 0, 2.0 * (double)gout->B * gout->D * gout->H * gout->W * 1024.0 * T);
-    wgrad_reduce(st, workspace, partial_db, slabs, T, dW, db, accumulate);
-    AS_CHECK_LAUNCH("as_conv32_wgrad(reduce)");
-    return AS_OK;
-  }
+int conv32_wgrad_generic_launch(const ConvWgradArgs& w, const as_pcl* gin, const as_pcl* gout, const as_conv_shape* s,
+                                const Wgrad32Plan& p, const char* who, void* stream) {
   WgradArgs a;
-  a.x = x; a.gz = gz; a.partial = workspace; a.partial_db = workspace + (int64_t)nchunks * T * 1024;
+  a.x = w.x; a.gz = w.gz; a.partial = w.partial; a.partial_db = w.partial_db;
   a.gin = as_make_dev(gin); a.gout = as_make_dev(gout);
-  a.nseg = wgrad_segments(gout, s, &a.seg_steps);
-  a.rows = gout->B * gout->D * gout->H * a.nseg; a.rows_per_chunk = rpc; a.nchunks = nchunks; a.ntaps = T; a.stride = s->stride;
-  if (int e = fill_taps(gin, s, a.tap_off, "as_conv32_wgrad")) return e;
+  a.nseg = p.nseg; a.seg_steps = p.seg_steps;
+  a.rows = gout->B * gout->D * gout->H * a.nseg; a.rows_per_chunk = p.rows_per_chunk; a.nchunks = p.nchunks; a.ntaps = p.T;
+  a.stride = s->stride;
+  if (int e = fill_taps(gin, s, a.tap_off, who)) return e;
   hipStream_t st = (hipStream_t)stream;
-  as_prof_mark(1, st, 1, 0.0);
-  if (tg == 3) launch_wgrad<3>(a, T / 3, nchunks, st);
-  else if (tg == 5) launch_wgrad<5>(a, T / 5, nchunks, st);
-  else launch_wgrad<1>(a, T, nchunks, st);
-  as_prof_mark(1, st, 0, 2.0 * (double)gout->B * gout->D * gout->H * gout->W * 1024.0 * T);
-  AS_CHECK_LAUNCH("as_conv32_wgrad");
-  wgrad_reduce(st, a.partial, a.partial_db, nchunks, T, dW, db, accumulate);
-  AS_CHECK_LAUNCH("as_conv32_wgrad(reduce)");
+  if (p.tap_group == 3) launch_wgrad<3>(a, p.T / 3, p.nchunks, st);
+  else if (p.tap_group == 5) launch_wgrad<5>(a, p.T / 5, p.nchunks, st);
+  else launch_wgrad<1>(a, p.T, p.nchunks, st);
   return AS_OK;
 }

@@ -17,7 +17,7 @@
 // share the launch.  Weights stream from L1/L2 one tap ahead (one coalesced KB per instruction, as before).
 // Same arithmetic per output as the generic kernels (taps in the same order, K in the same order): bit-identical results.
 #include "as_common.h"
-#include "conv32_s2.h"
+#include "conv_entry.h"
 
 struct S2Args {
   const float* x;        // forward: the input (PCL, halo >= 2); data gradient: the coarse gradient gz (PCL, halo >= 1)
@@ -135,15 +135,15 @@ bool conv32_s2_fwd_applicable(const as_pcl* gin, const as_pcl* gout, const as_co
   return (long)gout->B * gout->H * ((gout->W + 31) / 32) >= 1024;       // below: the split-K / generic kernels
 }
 
-int conv32_s2_fwd_launch(const float* x, const as_pcl* gin, const float* packed_w, const float* bias, float* z,
-                         const as_pcl* gout, void* stream) {
+int conv32_s2_fwd_launch(const ConvFwdArgs& f, const as_pcl* gin, const as_pcl* gout, const as_conv_shape*, const char* who,
+                         void* stream) {
   static AsPerDevice attr_set;
   S2Args a;
-  a.x = x; a.wp = packed_w; a.bias = bias; a.out = z; a.gin = as_make_dev(gin); a.gout = as_make_dev(gout);
+  a.x = f.x; a.wp = f.w; a.bias = f.bias; a.out = f.z; a.gin = as_make_dev(gin); a.gout = as_make_dev(gout);
   a.nseg = (gout->W + 31) / 32; a.ntiles = gout->B * gout->H * a.nseg;
   void* kargs[] = {&a};
   return as_launch_lds(reinterpret_cast<const void*>(conv32_s2_fwd_kernel), attr_set, 4 * S2F_WAVE, 4 * S2F_WAVE,
-                       dim3(as_div_up(a.ntiles, 4)), dim3(256), kargs, "as_conv32_fwd", (hipStream_t)stream);
+                       dim3(as_div_up(a.ntiles, 4)), dim3(256), kargs, who, (hipStream_t)stream);
 }
 
 // ---- data gradient: gx[2y'+py][2x'+px] from gz rows y'-1 .. y'+1 -------------------------------------------------------
@@ -230,12 +230,13 @@ bool conv32_s2_dgrad_applicable(const as_pcl* ggz, const as_pcl* ggx) {
   return (long)ggz->B * ggz->H * ((ggz->W + 31) / 32) >= 1024;
 }
 
-int conv32_s2_dgrad_launch(const float* gz, const as_pcl* ggz, const float* packed, float* gx, const as_pcl* ggx, void* stream) {
+int conv32_s2_dgrad_launch(const float* gz, const as_pcl* ggz, const float* packed, float* gx, const as_pcl* ggx, const char* who,
+                           void* stream) {
   static AsPerDevice attr_set;
   S2Args a;
   a.x = gz; a.wp = packed; a.bias = nullptr; a.out = gx; a.gin = as_make_dev(ggz); a.gout = as_make_dev(ggx);
   a.nseg = (ggz->W + 31) / 32; a.ntiles = ggz->B * ggz->H * a.nseg;
   void* kargs[] = {&a};
   return as_launch_lds(reinterpret_cast<const void*>(conv32_s2_dgrad_kernel), attr_set, 4 * S2D_WAVE, 4 * S2D_WAVE,
-                       dim3(as_div_up(a.ntiles, 4)), dim3(256), kargs, "as_conv32_dgrad_s2", (hipStream_t)stream);
+                       dim3(as_div_up(a.ntiles, 4)), dim3(256), kargs, who, (hipStream_t)stream);
 }

@@ -167,15 +167,10 @@ static int conv3d_tiles_per_plane(const as_pcl* g) {
 
 int conv3d_lds_grid(const as_pcl* gout) { return gout->B * gout->D * conv3d_tiles_per_plane(gout); }
 
-int conv3d_lds_launch(const float* x, const as_pcl* gin, const float* packed_w, const float* bias, float* z,
-                      const as_pcl* gout, int epilogue, const float* ep_scale, const float* ep_shift, float slope,
-                      const float* residual, float* stat_mean, float* stat_m2, float* stat_cnt, void* stream) {
+int conv3d_lds_launch(const ConvFwdArgs& f, const as_pcl* gin, const as_pcl* gout, const as_conv_shape*, const char* who,
+                      void* stream) {
   Conv3dLdsArgs a;
-  a.x = x; a.wq = packed_w;
-  a.ep.bias = bias; a.ep.z = z; a.ep.ep_scale = ep_scale; a.ep.ep_shift = ep_shift; a.ep.residual = residual;
-  a.ep.stat_mean = epilogue == 0 ? stat_mean : nullptr; a.ep.stat_m2 = epilogue == 0 ? stat_m2 : nullptr;
-  a.ep.stat_cnt = epilogue == 0 ? stat_cnt : nullptr;
-  a.ep.epilogue = epilogue; a.ep.slope = slope;
+  a.x = f.x; a.wq = f.w; a.ep = epilogue_args(f);
   a.g = as_make_dev(gin);
   a.tiles_per_plane = conv3d_tiles_per_plane(gin);
   a.npos = (gin->H - 1) * a.g.Wp + gin->W;
@@ -185,7 +180,7 @@ int conv3d_lds_launch(const float* x, const as_pcl* gin, const float* packed_w, 
   static AsPerDevice attr_set;
   void* kargs[] = {&a};
   return as_launch_lds(reinterpret_cast<const void*>(conv3d_lds_kernel), attr_set, 64 * 1024, lds_bytes, dim3(conv3d_lds_grid(gout)),
-                       dim3(256), kargs, "as_conv32_fwd(3-D LDS)", (hipStream_t)stream);
+                       dim3(256), kargs, who, (hipStream_t)stream);
 }
 
 
@@ -336,10 +331,10 @@ int conv3d_wgrad_lds_slabs(const as_pcl* gout) {
                                                            // (22 per XCD = 66 workgroups on 64 slots: a second round, 82 us for 50)
 }
 
-int conv3d_wgrad_lds_launch(const float* x, const as_pcl* gin, const float* gz, const as_pcl* gout,
-                            float* partial, float* partial_db, void* stream) {
+int conv3d_wgrad_lds_launch(const ConvWgradArgs& w, const as_pcl* gin, const as_pcl* gout, const as_conv_shape*,
+                            const char* who, void* stream) {
   Wgrad3dLdsArgs a;
-  a.x = x; a.gz = gz; a.partial = partial; a.partial_db = partial_db;
+  a.x = w.x; a.gz = w.gz; a.partial = w.partial; a.partial_db = w.partial_db;
   a.g = as_make_dev(gin);
   a.tiles_per_plane = conv3d_tiles_per_plane(gin);
   a.npos = (gin->H - 1) * a.g.Wp + gin->W;
@@ -351,5 +346,5 @@ int conv3d_wgrad_lds_launch(const float* x, const as_pcl* gin, const float* gz, 
   static AsPerDevice attr_set;
   void* kargs[] = {&a};
   return as_launch_lds(reinterpret_cast<const void*>(conv3d_wgrad_lds_kernel), attr_set, 80 * 1024, lds_bytes,
-                       dim3(8 * ((a.nchunks + 7) / 8) * 3), dim3(256), kargs, "as_conv32_wgrad(3-D LDS)", (hipStream_t)stream);
+                       dim3(8 * ((a.nchunks + 7) / 8) * 3), dim3(256), kargs, who, (hipStream_t)stream);
 }

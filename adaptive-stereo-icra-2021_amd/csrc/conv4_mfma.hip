@@ -164,17 +164,10 @@ __global__ __launch_bounds__(256, 2) void conv4_s2_fwd_kernel(Conv4S2Args p) {
   }
 }
 
-static bool conv4_s2_applicable(const as_pcl* gin, const as_pcl* gout, const as_conv_shape* s) {
+bool conv4_s2_applicable(const as_pcl* gin, const as_pcl* gout, const as_conv_shape* s) {
   if (s->kh != 5 || s->kw != 5 || s->stride != 2 || s->dil != 1 || s->pad_h != 2 || s->pad_w != 2) return false;
   if (gin->ph < 2 || gin->pw < 2) return false;            // rows 2y-2 .. 2y+2 and the left edge; the right edge is clamped
   return (long)gout->B * gout->H * ((gout->W + 31) / 32) >= 4096;
-}
-
-static bool g_conv4_s2 = true;
-extern "C" int as_conv4_s2_enable(int on) {                // 0 / 1; anything else only reads.  Returns the previous setting.
-  const int prev = g_conv4_s2 ? 1 : 0;
-  if (on == 0 || on == 1) g_conv4_s2 = on == 1;
-  return prev;
 }
 
 // ---- 3x3 stride-1 instance over row segments (the refinement's 4->32 input layer, full resolution) -------------
@@ -326,13 +319,13 @@ __global__ __launch_bounds__(256) void conv4_rows_kernel(Conv4RowsArgs p) {
   }
 }
 
-static bool conv4_rows_applicable(const as_pcl* gin, const as_pcl* gout, const as_conv_shape* s) {
+bool conv4_rows_applicable(const as_pcl* gin, const as_pcl* gout, const as_conv_shape* s) {
   return s->kh == 3 && s->kw == 3 && s->stride == 1 && s->dil == 1 && s->pad_h == 1 && s->pad_w == 1 &&
          gin->H == gout->H && gin->W == gout->W && gout->W >= 32 && gin->ph >= 1 && gin->pw >= 1 &&
          gin->W + 2 * gin->pw >= 64 &&                      // a 64-pixel DMA window fits into a padded row
          (long)gout->B * gout->H * ((gout->W + 31) / 32) < (1L << 31);
 }
-static int conv4_rows_grid(const as_pcl* gout) {
+int conv4_rows_grid(const as_pcl* gout) {
   const long nwt = (long)gout->B * gout->H * ((gout->W + 31) / 32);
   long g = (nwt + 3) / 4;
   if (g > 1024) g = 1024;      // 36 KB of LDS per workgroup: four resident per CU, all of them at once
@@ -889,12 +882,12 @@ __global__ __launch_bounds__(256, 4) void conv4_wgrad_mfma_kernel(Wgrad4RowsArgs
   if (t < 32) p.partial_db[blockIdx.x * 32 + t] = red[t] + red[32 + t] + red[64 + t] + red[96 + t];
 }
 
-static bool conv4_wgrad_rows_applicable(const as_pcl* gin, const as_pcl* gout, const as_conv_shape* s) {
+bool conv4_wgrad_rows_applicable(const as_pcl* gin, const as_pcl* gout, const as_conv_shape* s) {
   return s->kh == 3 && s->kw == 3 && s->stride == 1 && s->dil == 1 && s->pad_h == 1 && s->pad_w == 1 &&
          gin->H == gout->H && gin->W == gout->W && gin->ph >= 1 && gin->pw >= 1 &&
          (long)gout->B * gout->H * ((gout->W + 127) / 128) < (1L << 31);
 }
-static int conv4_wgrad_rows_grid(const as_pcl* gout) {
+int conv4_wgrad_rows_grid(const as_pcl* gout) {
   const long nch = (long)gout->B * gout->H * ((gout->W + 127) / 128);
   long g = (nch + 3) / 4;
   if (g > 1024) g = 1024;
@@ -944,31 +937,7 @@ __global__ __launch_bounds__(1024) void conv4_wgrad_reduce_kernel(const float* _
   }
 }
 
-// ---- host -------------------------------------------------------------------------------------------------
-static int fill_taps4(const as_pcl* gin, const as_conv_shape* s, int* tap_off) {
-  const int Wp = gin->W + 2 * gin->pw;
-  int n = 0;
-  for (int j = 0; j < s->kh; ++j)
-    for (int l = 0; l < s->kw; ++l) tap_off[n++] = (j * s->dil - s->pad_h) * Wp + (l * s->dil - s->pad_w);
-  return n;
-}
-
-static int check4(const as_pcl* gin, const as_pcl* gout, const as_conv_shape* s, const char* who) {
-  AS_CHECK_ARG(gin && gout && s && as_pcl_ok(gout), "%s: bad geometry", who);
-  AS_CHECK_ARG(gin->D == 1 && gout->D == 1 && gin->pd == 0 && gout->pd == 0 && s->kd == 1, "%s: 2-D only", who);
-  AS_CHECK_ARG(gin->B == gout->B && gin->B > 0 && gin->H > 0 && gin->W > 0, "%s: bad input extent", who);
-  const int T = s->kh * s->kw;
-  AS_CHECK_ARG(T >= 1 && T <= AS_MAX_TAPS && s->dil >= 1 && s->stride >= 1, "%s: unsupported kernel", who);
-  const int eh = (gin->H + 2 * s->pad_h - s->dil * (s->kh - 1) - 1) / s->stride + 1;
-  const int ew = (gin->W + 2 * s->pad_w - s->dil * (s->kw - 1) - 1) / s->stride + 1;
-  AS_CHECK_ARG(eh == gout->H && ew == gout->W, "%s: output extent mismatch", who);
-  const int hi_h = (gout->H - 1) * s->stride + s->dil * (s->kh - 1) - s->pad_h - (gin->H - 1);
-  const int hi_w = (gout->W - 1) * s->stride + s->dil * (s->kw - 1) - s->pad_w - (gin->W - 1);
-  AS_CHECK_ARG(s->pad_h <= gin->ph && s->pad_w <= gin->pw && hi_h <= gin->ph && hi_w <= gin->pw,
-               "%s: input halo too small", who);
-  return AS_OK;
-}
-
+// ---- host: packing, one launcher per kernel family (entry points, checks and route decisions: conv_entry.hip) ------------
 extern "C" int64_t as_pcl4_numel(const as_pcl* g) {
   if (!g) return -1;
   return (int64_t)g->B * (g->H + 2 * g->ph) * (g->W + 2 * g->pw) * 4;
@@ -993,69 +962,41 @@ extern "C" int as_conv4_pack_weights(const float* w, int Cin, float* packed, con
   return AS_OK;
 }
 
-// Number of BatchNorm partials as_conv4_fwd writes for this configuration.
-extern "C" int as_conv4_stat_parts(const as_pcl* gin, const as_pcl* gout, const as_conv_shape* s) {
-  if (!gin || !gout || !s || !as_pcl_ok(gout)) return AS_ERR_ARG;
-  if (conv4_rows_applicable(gin, gout, s)) return conv4_rows_grid(gout);
-  return as_div_up((int64_t)gout->B * gout->H * gout->W, 128);
+int conv4_rows_launch(const ConvFwdArgs& f, const as_pcl* gin, const as_pcl* gout, const as_conv_shape*, const char*,
+                      void* stream) {
+  Conv4RowsArgs r;
+  r.x4 = f.x; r.wp = f.w; r.ep = epilogue_args(f);
+  r.gin = as_make_dev(gin); r.gout = as_make_dev(gout);
+  r.wtiles_per_row = (gout->W + 31) / 32;
+  r.nwtiles = gout->B * gout->H * r.wtiles_per_row;
+  const int grid = conv4_rows_grid(gout);
+  hipStream_t st = (hipStream_t)stream;
+  if (f.epilogue == 1) hipLaunchKernelGGL(conv4_rows_kernel<1>, dim3(grid), dim3(256), 0, st, r);
+  else if (r.ep.stat_mean) hipLaunchKernelGGL(conv4_rows_kernel<0>, dim3(grid), dim3(256), 0, st, r);
+  else hipLaunchKernelGGL(conv4_rows_kernel<2>, dim3(grid), dim3(256), 0, st, r);
+  return AS_OK;
 }
 
-// Whether as_conv4_fwd launches conv4_s2_fwd_kernel (the entry point's own test; as_conv4_s2_ok answers it for a plain epilogue
-// without moments).
-static bool conv4_s2_takes(const as_pcl* gin, const as_pcl* gout, const as_conv_shape* s, int epilogue, bool moments) {
-  return !conv4_rows_applicable(gin, gout, s) && g_conv4_s2 && epilogue == 0 && !moments && conv4_s2_applicable(gin, gout, s);
-}
-extern "C" int as_conv4_s2_ok(const as_pcl* gin, const as_pcl* gout, const as_conv_shape* s) {
-  if (check4(gin, gout, s, "as_conv4_s2_ok")) return AS_ERR_ARG;
-  return conv4_s2_takes(gin, gout, s, 0, false) ? 1 : 0;
+int conv4_s2_fwd_launch(const ConvFwdArgs& f, const as_pcl* gin, const as_pcl* gout, const as_conv_shape*, const char*,
+                        void* stream) {
+  Conv4S2Args q;
+  q.x4 = f.x; q.wp = f.w; q.bias = f.bias; q.z = f.z; q.gin = as_make_dev(gin); q.gout = as_make_dev(gout);
+  q.nseg = (gout->W + 31) / 32; q.ntiles = gout->B * gout->H * q.nseg;
+  hipLaunchKernelGGL(conv4_s2_fwd_kernel, dim3(512), dim3(256), 0, (hipStream_t)stream, q);   // two workgroups per CU (180 registers; three with 168 and two spilled: 78 us against 75)
+  return AS_OK;
 }
 
-extern "C" int as_conv4_fwd(const float* x4, const as_pcl* gin, const float* packed_w, const float* bias,
-                            float* z, const as_pcl* gout, const as_conv_shape* s,
-                            int epilogue, const float* ep_scale, const float* ep_shift, float slope,
-                            float* stat_mean, float* stat_m2, float* stat_cnt, void* stream) {
-  if (int e = check4(gin, gout, s, "as_conv4_fwd")) return e;
-  AS_CHECK_ARG(x4 && packed_w && z, "as_conv4_fwd: null pointer");
-  AS_CHECK_ARG(epilogue_args_ok(epilogue, ep_scale, ep_shift, stat_mean, stat_m2, stat_cnt), "as_conv4_fwd: bad epilogue arguments");
-  if (conv4_rows_applicable(gin, gout, s)) {
-    Conv4RowsArgs r;
-    r.x4 = x4; r.wp = packed_w;
-    r.ep.bias = bias; r.ep.z = z; r.ep.ep_scale = ep_scale; r.ep.ep_shift = ep_shift; r.ep.residual = nullptr;
-    r.ep.stat_mean = epilogue == 0 ? stat_mean : nullptr; r.ep.stat_m2 = epilogue == 0 ? stat_m2 : nullptr;
-    r.ep.stat_cnt = epilogue == 0 ? stat_cnt : nullptr;
-    r.ep.epilogue = epilogue; r.ep.slope = slope;
-    r.gin = as_make_dev(gin); r.gout = as_make_dev(gout);
-    r.wtiles_per_row = (gout->W + 31) / 32;
-    r.nwtiles = gout->B * gout->H * r.wtiles_per_row;
-    const int grid = conv4_rows_grid(gout);
-    hipStream_t st = (hipStream_t)stream;
-    if (epilogue == 1) hipLaunchKernelGGL(conv4_rows_kernel<1>, dim3(grid), dim3(256), 0, st, r);
-    else if (r.ep.stat_mean) hipLaunchKernelGGL(conv4_rows_kernel<0>, dim3(grid), dim3(256), 0, st, r);
-    else hipLaunchKernelGGL(conv4_rows_kernel<2>, dim3(grid), dim3(256), 0, st, r);
-    AS_CHECK_LAUNCH("as_conv4_fwd(rows)");
-    return AS_OK;
-  }
-  if (conv4_s2_takes(gin, gout, s, epilogue, stat_mean != nullptr)) {
-    Conv4S2Args q;
-    q.x4 = x4; q.wp = packed_w; q.bias = bias; q.z = z; q.gin = as_make_dev(gin); q.gout = as_make_dev(gout);
-    q.nseg = (gout->W + 31) / 32; q.ntiles = gout->B * gout->H * q.nseg;
-    hipLaunchKernelGGL(conv4_s2_fwd_kernel, dim3(512), dim3(256), 0, (hipStream_t)stream, q);   // two workgroups per CU (180 registers; three with 168 and two spilled: 78 us against 75)
-    AS_CHECK_LAUNCH("as_conv4_fwd(5x5 stride 2, staged rows)");
-    return AS_OK;
-  }
+int conv4_generic_launch(const ConvFwdArgs& f, const as_pcl* gin, const as_pcl* gout, const as_conv_shape* s, const char* who,
+                         void* stream) {
   Conv4Args a;
-  a.x4 = x4; a.wp = packed_w;
-  a.ep.bias = bias; a.ep.z = z; a.ep.ep_scale = ep_scale; a.ep.ep_shift = ep_shift; a.ep.residual = nullptr;
-  a.ep.stat_mean = epilogue == 0 ? stat_mean : nullptr; a.ep.stat_m2 = epilogue == 0 ? stat_m2 : nullptr;
-  a.ep.stat_cnt = epilogue == 0 ? stat_cnt : nullptr;
-  a.ep.epilogue = epilogue; a.ep.slope = slope;
+  a.x4 = f.x; a.wp = f.w; a.ep = epilogue_args(f);
   a.gin = as_make_dev(gin); a.gout = as_make_dev(gout);
   const int64_t M = (int64_t)gout->B * gout->H * gout->W;
-  a.M = (int)M; a.stride = s->stride; a.ntaps = fill_taps4(gin, s, a.tap_off);
+  a.M = (int)M; a.stride = s->stride; a.ntaps = s->kh * s->kw;
+  if (int e = fill_taps(gin, s, a.tap_off, who)) return e;
   if (a.ntaps == 25) hipLaunchKernelGGL(conv4_fwd_kernel<25>, dim3(as_div_up(M, 128)), dim3(256), 0, (hipStream_t)stream, a);
   else if (a.ntaps == 9) hipLaunchKernelGGL(conv4_fwd_kernel<9>, dim3(as_div_up(M, 128)), dim3(256), 0, (hipStream_t)stream, a);
   else hipLaunchKernelGGL(conv4_fwd_kernel<0>, dim3(as_div_up(M, 128)), dim3(256), 0, (hipStream_t)stream, a);
-  AS_CHECK_LAUNCH("as_conv4_fwd");
   return AS_OK;
 }
 
@@ -1065,36 +1006,19 @@ extern "C" int as_conv4_fwd(const float* x4, const as_pcl* gin, const float* pac
 // round of resident workgroups: with 64-step units and 1024 wanted chunks the 5x5 layer at the bench workload was 940
 // workgroups of two units per wave on 768 slots (157 registers: three workgroups per CU) — a second round for a fifth of the
 // work: 82 us for the matrix instructions alone where 49 are nominal (tests/tools/exp_step.sh, -DC4W_EXP_NOLOAD).
-static int plan4_segments(const as_pcl* gout) { return (((gout->W + 1) >> 1) + W4_SEG_STEPS - 1) / W4_SEG_STEPS; }
-static bool plan4_staged_shape(const as_conv_shape* s) {     // the 5x5 stride-2 first layer (conv4_s2_wgrad_kernel)
-  return s->kh == 5 && s->kw == 5 && s->stride == 2 && s->dil == 1 && s->pad_h == 2 && s->pad_w == 2;
-}
-static void plan4(const as_pcl* gout, const as_conv_shape* s, bool staged, int* nb, int* rpc, int* nchunks) {
-  const int T = s->kh * s->kw;
-  *nb = (4 * T + 31) / 32;
-  const int units = gout->B * gout->H * plan4_segments(gout);
+Wgrad4Plan conv4_wgrad_plan(const as_pcl* gout, const as_conv_shape* s, bool staged) {
+  Wgrad4Plan p;
+  p.nb = (4 * s->kh * s->kw + 31) / 32;
+  p.nseg = (((gout->W + 1) >> 1) + W4_SEG_STEPS - 1) / W4_SEG_STEPS;
+  const int units = gout->B * gout->H * p.nseg;
   // resident workgroups (the register count decides): the staged-row kernel runs two per CU
-  const int slots = staged ? 512 : (*nb >= 3 ? 768 : 1024);
+  const int slots = staged ? 512 : (p.nb >= 3 ? 768 : 1024);
   int r = (units + slots - 1) / slots;
   r = (r + 3) / 4 * 4;
   if (r < 4) r = 4;
-  *rpc = r;
-  *nchunks = (units + r - 1) / r;
-}
-
-extern "C" int64_t as_conv4_wgrad_workspace(const as_pcl* gout, const as_conv_shape* s) {
-  if (!gout || !s || !as_pcl_ok(gout)) return -1;
-  int nb, rpc, nchunks;
-  plan4(gout, s, false, &nb, &rpc, &nchunks);               // (the larger of the two plans: as_conv4_s2_enable may change in between)
-  int64_t need = (int64_t)nchunks * nb * 1024 + (int64_t)nchunks * 32;
-  if (plan4_staged_shape(s)) {
-    plan4(gout, s, true, &nb, &rpc, &nchunks);
-    const int64_t n2 = (int64_t)nchunks * nb * 1024 + (int64_t)nchunks * 32;
-    if (n2 > need) need = n2;
-  }
-  const int64_t rows_need = (int64_t)conv4_wgrad_rows_grid(gout) * (2048 + 32);     // the 3x3 stride-1 instance
-  if (s->kh == 3 && s->kw == 3 && s->stride == 1 && rows_need > need) need = rows_need;
-  return need;
+  p.rows_per_chunk = r;
+  p.nchunks = (units + r - 1) / r;
+  return p;
 }
 
 template <int NB>
@@ -1103,60 +1027,29 @@ static void launch4(const Wgrad4Args& a, int nchunks, hipStream_t st) {
   hipLaunchKernelGGL(conv4_wgrad_kernel<NB>, dim3(nchunks), dim3(256), lds, st, a);
 }
 
-static int conv4_wgrad_rows_launch(const float* x4, const as_pcl* gin, const float* gz, const as_pcl* gout, int Cin,
-                                   float* dW, float* db, int accumulate, float* workspace, bool apply,
-                                   const float* bn_z, const float* scale, const float* shift, const float* mean,
-                                   const float* coef, float slope, float* gz_out, void* stream,
-                                   const float* w_proj = nullptr, float* h_out = nullptr) {
+// w.bn: stage 3 of the layer's BatchNorm backward on the way in, g_z written (gz_out) or projected (w_proj, h_out)
+int conv4_wgrad_rows_launch(const ConvWgradArgs& w, const as_pcl* gin, const as_pcl* gout, const as_conv_shape*, const char*,
+                            void* stream) {
+  static const WgradBnApply none = {};
+  const WgradBnApply& bn = w.bn ? *w.bn : none;
   Wgrad4RowsArgs r;
-  const int grid = conv4_wgrad_rows_grid(gout);
-  r.x4 = x4; r.gz = gz; r.partial = workspace; r.partial_db = workspace + (int64_t)grid * 2048;
+  r.x4 = w.x; r.gz = w.gz; r.partial = w.partial; r.partial_db = w.partial_db;
   r.gin = as_make_dev(gin); r.gout = as_make_dev(gout);
   r.chunks_per_row = (gout->W + 127) / 128; r.nchunks = gout->B * gout->H * r.chunks_per_row;
-  r.bn_z = bn_z; r.bn_scale = scale; r.bn_shift = shift; r.bn_mean = mean; r.bn_coef = coef; r.gz_out = gz_out; r.slope = slope;
+  r.bn_z = bn.z; r.bn_scale = bn.scale; r.bn_shift = bn.shift; r.bn_mean = bn.mean; r.bn_coef = bn.coef; r.gz_out = bn.gz_out;
+  r.slope = bn.slope; r.w_proj = bn.w_proj; r.h_out = bn.h_out;
+  const int grid = conv4_wgrad_rows_grid(gout);
   hipStream_t st = (hipStream_t)stream;
-  r.w_proj = w_proj; r.h_out = h_out;
-  if (apply && w_proj) hipLaunchKernelGGL(conv4_wgrad_mfma_kernel<true>, dim3(grid), dim3(256), 0, st, r);   // grid <= 1,024 = 4 per CU
-  else if (apply) hipLaunchKernelGGL((conv4_wgrad_rows_kernel<true, false>), dim3(grid), dim3(256), 0, st, r);
+  if (w.bn && bn.w_proj) hipLaunchKernelGGL(conv4_wgrad_mfma_kernel<true>, dim3(grid), dim3(256), 0, st, r);   // grid <= 1,024 = 4 per CU
+  else if (w.bn) hipLaunchKernelGGL((conv4_wgrad_rows_kernel<true, false>), dim3(grid), dim3(256), 0, st, r);
   else hipLaunchKernelGGL((conv4_wgrad_rows_kernel<false, false>), dim3(grid), dim3(256), 0, st, r);
-  AS_CHECK_LAUNCH("as_conv4_wgrad(rows)");
-  hipLaunchKernelGGL(conv4_wgrad_reduce_kernel, dim3(as_div_up(4 * 9 * 32 + 32, 64)), dim3(1024), 0, st, r.partial,
-                     r.partial_db, grid, 2, 9, Cin, dW, db, accumulate);
-  AS_CHECK_LAUNCH("as_conv4_wgrad(reduce)");
   return AS_OK;
 }
 
-// Weight gradient fused with stage 3 of the layer's BatchNorm backward (see as_conv32_wgrad_bnapply).
-extern "C" int as_conv4_wgrad_bnapply_ok(const as_pcl* gin, const as_pcl* gout, const as_conv_shape* s) {
-  if (!gin || !gout || !s || !as_pcl_ok(gout)) return AS_ERR_ARG;
-  return conv4_wgrad_rows_applicable(gin, gout, s) ? 1 : 0;
-}
-
-extern "C" int as_conv4_wgrad_bnapply(const float* x4, const as_pcl* gin, const float* g_a, const float* z,
-                                      const as_pcl* gout, const as_conv_shape* s, int Cin, const float* scale,
-                                      const float* shift, const float* mean, const float* coef, float slope, float* g_z,
-                                      float* dW, float* db, int accumulate, float* workspace, void* stream) {
-  if (int e = check4(gin, gout, s, "as_conv4_wgrad_bnapply")) return e;
-  AS_CHECK_ARG(x4 && g_a && z && scale && shift && mean && coef && g_z && dW && workspace && Cin >= 1 && Cin <= 4,
-               "as_conv4_wgrad_bnapply: bad argument");
-  AS_CHECK_ARG(conv4_wgrad_rows_applicable(gin, gout, s), "as_conv4_wgrad_bnapply: configuration not supported");
-  return conv4_wgrad_rows_launch(x4, gin, g_a, gout, Cin, dW, db, accumulate, workspace, true, z, scale, shift, mean, coef,
-                                 slope, g_z, stream);
-}
-
-// As as_conv4_wgrad_bnapply, but g_z is not written: the nine per-tap projections h[t][p] = sum_co g_z[p][co] * w_proj[t][co]
-// are ([B][9][H][W]), which is all a following 3x3 32->1 data gradient needs (as_tap_gather sums the nine shifted planes).
-extern "C" int as_conv4_wgrad_bnapply_proj(const float* x4, const as_pcl* gin, const float* g_a, const float* z,
-                                           const as_pcl* gout, const as_conv_shape* s, int Cin, const float* scale,
-                                           const float* shift, const float* mean, const float* coef, float slope,
-                                           const float* w_proj, float* h, float* dW, float* db, int accumulate,
-                                           float* workspace, void* stream) {
-  if (int e = check4(gin, gout, s, "as_conv4_wgrad_bnapply_proj")) return e;
-  AS_CHECK_ARG(x4 && g_a && z && scale && shift && mean && coef && w_proj && h && dW && workspace && Cin >= 1 && Cin <= 4,
-               "as_conv4_wgrad_bnapply_proj: bad argument");
-  AS_CHECK_ARG(conv4_wgrad_rows_applicable(gin, gout, s), "as_conv4_wgrad_bnapply_proj: configuration not supported");
-  return conv4_wgrad_rows_launch(x4, gin, g_a, gout, Cin, dW, db, accumulate, workspace, true, z, scale, shift, mean, coef,
-                                 slope, nullptr, stream, w_proj, h);
+void conv4_wgrad_reduce_launch(const float* partial, const float* partial_db, int nchunks, int nb, int T, int Cin, float* dW,
+                               float* db, int accumulate, void* stream) {
+  hipLaunchKernelGGL(conv4_wgrad_reduce_kernel, dim3(as_div_up(4 * T * 32 + 32, 64)), dim3(1024), 0, (hipStream_t)stream, partial,
+                     partial_db, nchunks, nb, T, Cin, dW, db, accumulate);
 }
 
 // out[b][y][x] = residual[b][y][x] + sum_t h[b][t][y + t/3 - 1][x + t%3 - 1]   (zero outside the image)
@@ -1182,40 +1075,27 @@ extern "C" int as_tap_gather(const float* h, const float* residual, float* out, 
   return AS_OK;
 }
 
-extern "C" int as_conv4_wgrad(const float* x4, const as_pcl* gin, const float* gz, const as_pcl* gout,
-                              const as_conv_shape* s, int Cin, float* dW, float* db, int accumulate, float* workspace,
-                              void* stream) {
-  if (int e = check4(gin, gout, s, "as_conv4_wgrad")) return e;
-  AS_CHECK_ARG(x4 && gz && dW && workspace && Cin >= 1 && Cin <= 4, "as_conv4_wgrad: bad argument");
-  if (conv4_wgrad_rows_applicable(gin, gout, s))
-    return conv4_wgrad_rows_launch(x4, gin, gz, gout, Cin, dW, db, accumulate, workspace, false, nullptr, nullptr, nullptr,
-                                   nullptr, nullptr, 0.f, nullptr, stream);
-  int nb, rpc, nchunks;
-  const bool staged = g_conv4_s2 && plan4_staged_shape(s) && gin->ph >= 2 && gin->pw >= 2;
-  plan4(gout, s, staged, &nb, &rpc, &nchunks);
-  AS_CHECK_ARG(nb >= 1 && nb <= 4, "as_conv4_wgrad: kernel too large");
+
+// staged: the 5x5 stride-2 first layer of the feature towers, input rows staged in LDS (conv4_s2_wgrad_kernel)
+int conv4_wgrad_generic_launch(const ConvWgradArgs& w, const as_pcl* gin, const as_pcl* gout, const as_conv_shape* s,
+                               const Wgrad4Plan& p, bool staged, const char* who, void* stream) {
   Wgrad4Args a;
-  a.x4 = x4; a.gz = gz; a.partial = workspace; a.partial_db = workspace + (int64_t)nchunks * nb * 1024;
+  a.x4 = w.x; a.gz = w.gz; a.partial = w.partial; a.partial_db = w.partial_db;
   a.gin = as_make_dev(gin); a.gout = as_make_dev(gout);
-  a.nseg = plan4_segments(gout);
-  a.rows = gout->B * gout->H * a.nseg; a.rows_per_chunk = rpc; a.stride = s->stride;
-  a.ntaps = fill_taps4(gin, s, a.tap_off);
+  a.nseg = p.nseg;
+  a.rows = gout->B * gout->H * a.nseg; a.rows_per_chunk = p.rows_per_chunk; a.stride = s->stride;
+  a.ntaps = s->kh * s->kw;
+  if (int e = fill_taps(gin, s, a.tap_off, who)) return e;
   hipStream_t st = (hipStream_t)stream;
   if (staged) {
-    // (the 5x5 stride-2 first layer of the feature towers: input rows staged in LDS)
     const size_t lds = (size_t)(3 * 4 * 16 * 64 + 4 * 32) * sizeof(float);      // >= 4 * C4W_WAVE_BYTES
-    hipLaunchKernelGGL(conv4_s2_wgrad_kernel, dim3(nchunks), dim3(256), lds, st, a);
+    hipLaunchKernelGGL(conv4_s2_wgrad_kernel, dim3(p.nchunks), dim3(256), lds, st, a);
   } else
-  switch (nb) {
-    case 1: launch4<1>(a, nchunks, st); break;
-    case 2: launch4<2>(a, nchunks, st); break;
-    case 3: launch4<3>(a, nchunks, st); break;
-    default: launch4<4>(a, nchunks, st); break;
+  switch (p.nb) {
+    case 1: launch4<1>(a, p.nchunks, st); break;
+    case 2: launch4<2>(a, p.nchunks, st); break;
+    case 3: launch4<3>(a, p.nchunks, st); break;
+    default: launch4<4>(a, p.nchunks, st); break;
   }
-  AS_CHECK_LAUNCH("as_conv4_wgrad");
-  const int T = a.ntaps;
-  hipLaunchKernelGGL(conv4_wgrad_reduce_kernel, dim3(as_div_up(4 * T * 32 + 32, 64)), dim3(1024), 0, st, a.partial,
-                     a.partial_db, nchunks, nb, T, Cin, dW, db, accumulate);
-  AS_CHECK_LAUNCH("as_conv4_wgrad(reduce)");
   return AS_OK;
 }

@@ -4,6 +4,7 @@
 // Stores are 128-byte voxel lines (32 lanes x 4 B), two lines per store instruction.
 #pragma once
 #include "as_common.h"
+#include "conv_entry.h"
 
 // 64 floats that swallow stores a kernel issues only to keep its per-wave store count exact (conv4_mfma.hip)
 static __device__ float as_store_dump[64];     // one copy per translation unit (no relocatable device code)
@@ -138,9 +139,13 @@ __device__ inline void conv_decode(int vc, const PclDev& gin, const PclDev& gout
   out_vox = (int)gout.vox(b, d, y * m.out_stride + m.out_oy, x * m.out_stride + m.out_ox);
 }
 
-static inline int epilogue_args_ok(int epilogue, const float* sc, const float* sh, const float* sm, const float* s2,
-                                   const float* cnt) {
-  if (!(epilogue == 0 || (epilogue == 1 && sc && sh))) return 0;
-  if ((sm == nullptr) != (s2 == nullptr) || (sm == nullptr) != (cnt == nullptr)) return 0;
-  return 1;
+// What a launcher hands its kernel of an entry point's forward block (conv_entry.h).  The moments pass only for epilogue 0:
+// the kernels test stat_mean alone.
+static inline EpilogueArgs epilogue_args(const ConvFwdArgs& f) {
+  EpilogueArgs e;
+  e.bias = f.bias; e.z = f.z; e.ep_scale = f.scale; e.ep_shift = f.shift; e.residual = f.residual;
+  e.stat_mean = f.epilogue == 0 ? f.stat_mean : nullptr; e.stat_m2 = f.epilogue == 0 ? f.stat_m2 : nullptr;
+  e.stat_cnt = f.epilogue == 0 ? f.stat_cnt : nullptr;
+  e.epilogue = f.epilogue; e.slope = f.slope;
+  return e;
 }

@@ -141,6 +141,7 @@ _SIGNATURES = {
                                   c_vp, c_vp]),
   "as_agg3d_ok": (c_int, [_P(Pcl)]),
   "as_agg3d_parts": (c_int, [_P(Pcl)]),
+  "as_agg3d_plan": (c_int, [_P(Pcl), c_vp]),
   "as_agg3d_fwd": (c_int, [c_vp, _P(Pcl), c_vp, c_vp, c_vp, c_vp, _P(BnMerge), c_vp, c_vp, c_int, c_vp, c_vp, c_float, c_vp, c_vp,
                            c_vp, c_vp]),
   "as_trunk_parts": (c_int, [_P(Pcl), c_int]),

@@ -428,8 +428,33 @@ static int agg_launch_t(const Agg3dArgs& a, int lds_bytes, hipStream_t st) {
   return a.strips > 1 ? agg_launch_s<IN, EPI, true>(a, lds_bytes, st) : agg_launch_s<IN, EPI, false>(a, lds_bytes, st);
 }
 
+// The part of the argument block that follows from the geometry alone: the strip plan, the tiling of a (sub-)plane, the staged
+// run, the segments and the units.  The launcher and as_agg3d_plan.
+static void agg_fill_plan(const as_pcl* g, Agg3dArgs& a) {
+  a.strips = agg_strips(g); a.Ws = agg_ws(g); a.tiles_per_strip = agg_tiles_per_strip(g);
+  a.tiles_per_plane = agg_tiles_per_plane(g);
+  a.npos = (g->H - 1) * a.Ws + (a.strips == 1 ? g->W : a.Ws - 2);
+  a.run = agg_run(g);
+  a.groups = (a.run + 7) / 8;
+  a.slot_bytes = a.groups * 1024;
+  a.seg_len = agg_seg_len(g);
+  a.nseg = as_div_up(g->D, a.seg_len);
+  a.units = g->B * a.tiles_per_plane * a.nseg;
+  a.per_xcd = as_div_up(a.units, 8);
+  a.wp_magic = (unsigned)((((uint64_t)1 << 32) + a.Ws - 1) / a.Ws);
+}
+
 extern "C" int as_agg3d_ok(const as_pcl* g) { return agg3d_applicable(g) ? 1 : 0; }
 extern "C" int as_agg3d_parts(const as_pcl* g) { return agg3d_applicable(g) ? agg3d_units(g) : AS_ERR_ARG; }
+extern "C" int as_agg3d_plan(const as_pcl* g, int out[8]) {
+  AS_CHECK_ARG(out != nullptr, "as_agg3d_plan: null pointer");
+  if (!agg3d_applicable(g)) return 0;
+  Agg3dArgs a;
+  agg_fill_plan(g, a);
+  out[0] = a.strips; out[1] = a.Ws; out[2] = a.tiles_per_strip; out[3] = a.npos;
+  out[4] = a.run; out[5] = a.seg_len; out[6] = a.nseg; out[7] = a.units;
+  return 1;
+}
 
 extern "C" int as_agg3d_fwd(const float* x, const as_pcl* g, const float* packed_w, const float* bias,
                             const float* in_scale, const float* in_shift, const as_bn_merge* in_bn, float* a_out,
@@ -455,17 +480,7 @@ extern "C" int as_agg3d_fwd(const float* x, const as_pcl* g, const float* packed
   a.ep.stat_cnt = moments ? stat_cnt : nullptr;
   a.ep.epilogue = epilogue; a.ep.slope = slope;
   a.g = as_make_dev(g);
-  a.strips = agg_strips(g); a.Ws = agg_ws(g); a.tiles_per_strip = agg_tiles_per_strip(g);
-  a.tiles_per_plane = agg_tiles_per_plane(g);
-  a.npos = (g->H - 1) * a.Ws + (a.strips == 1 ? g->W : a.Ws - 2);
-  a.run = agg_run(g);
-  a.groups = (a.run + 7) / 8;
-  a.slot_bytes = a.groups * 1024;
-  a.seg_len = agg_seg_len(g);
-  a.nseg = as_div_up(g->D, a.seg_len);
-  a.units = g->B * a.tiles_per_plane * a.nseg;
-  a.per_xcd = as_div_up(a.units, 8);
-  a.wp_magic = (unsigned)((((uint64_t)1 << 32) + a.Ws - 1) / a.Ws);
+  agg_fill_plan(g, a);
   const int lds_bytes = 4 * a.slot_bytes + 4096;
   hipStream_t st = (hipStream_t)stream;
   const double flops = 2.0 * (double)g->B * g->D * g->H * g->W * 1024.0 * 27.0;

@@ -275,6 +275,11 @@ typedef struct as_bn_merge {
 } as_bn_merge;
 int as_agg3d_ok(const as_pcl* g);
 int as_agg3d_parts(const as_pcl* g);
+/* read-only plan query, from the helper the launcher fills its argument block with: out = {strips, Ws (row pitch of the staged
+ * (sub-)plane), tiles per strip, npos (positions of a (sub-)plane from its first to its last interior voxel), run (staged voxels
+ * per plane), seg_len (output planes per unit), nseg, units}; the grid is 8 * ceil(units / 8) workgroups.  Returns 1, or 0
+ * where as_agg3d_ok(g) == 0 (out untouched).  Every plan gives equal outputs by design: only the query tells which one ran. */
+int as_agg3d_plan(const as_pcl* g, int out[8]);
 int as_agg3d_fwd(const float* x, const as_pcl* g, const float* packed_w, const float* bias,
                  const float* in_scale, const float* in_shift, const as_bn_merge* in_bn, float* a_out,
                  float* z, int epilogue, const float* ep_scale, const float* ep_shift, float slope,

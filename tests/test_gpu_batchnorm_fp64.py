@@ -408,7 +408,8 @@ def test_wino_moments_at_32_pairs():
     torch.cuda.empty_cache()
 
 
-AGG_GEOMS = [(1, 12, 24, 78), (3, 5, 9, 40), (1, 1, 4, 33), (2, 7, 6, 81), (4, 12, 24, 78)]
+AGG_GEOMS = [(1, 12, 24, 78), (3, 5, 9, 40), (1, 1, 4, 33), (2, 7, 6, 81), (4, 12, 24, 78),
+             (1, 2, 3, 120), (1, 2, 2, 156)]      # column strips: the second right-aligned over 4 overlap columns; no overlap
 
 
 @pytest.mark.parametrize("B,D,H,W", AGG_GEOMS)

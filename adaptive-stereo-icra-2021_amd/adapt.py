@@ -28,6 +28,25 @@ TRIALS_COLUMNS = ("trial", "step") + tuple(m + "_ADAPT" for m in METRIC_NAMES) +
     ("GRADIENT_UPDATES",)
 
 
+LEFTRIGHT_LOSS_MESSAGE = ("--leftright_consistency: the reference's left-right path cannot run (adapt.py:319 reads the "
+                          "misspelt opt.stereonet_intput_scale, and monodepth_leftright_loss overwrites its own outputs "
+                          "argument: SURVEY.md 0.8), so there is no behaviour to reproduce")
+
+
+def predict_disparity_leftright(feature_net, stereo_net, left, right, adapt_state, opt):
+  """Reference adapt.py:40-62: the left AND the right disparity maps of a batch from one pass over the mirrored batches, keys
+  ``..._l/..`` and ``..._r/..``.  The inference half runs (adaptive_stereo.consistency) for State.VALIDATION and State.DONE, the two
+  states in which the reference computes no gradients and has its networks in eval mode; State.IN_PROGRESS would feed the
+  reference's dead left-right loss and raises as the flag does; anything else is not a state."""
+  from adaptive_stereo.consistency import predict_disparity_leftright as both_views
+  from adaptive_stereo.control import State
+  if adapt_state == State.IN_PROGRESS:
+    raise NotImplementedError(LEFTRIGHT_LOSS_MESSAGE)
+  if adapt_state not in (State.VALIDATION, State.DONE):
+    raise ValueError("predict_disparity_leftright: adapt_state %r (State.VALIDATION or State.DONE)" % (adapt_state,))
+  return both_views(feature_net, stereo_net, left, right, output_cost_volume=True)
+
+
 def read_trials(path):
   """Rows of a trials.csv as dictionaries of strings ([] when the file does not exist)."""
   if not os.path.exists(path):
@@ -59,9 +78,7 @@ def adapt(opt, adapt_dataset=None, adapt_val_dataset=None, train_val_dataset=Non
   from adaptive_stereo.models.stereo_net import StereoNet, FeatureExtractorNetwork
 
   if opt.leftright_consistency:
-    raise NotImplementedError("--leftright_consistency: the reference's left-right path cannot run (adapt.py:319 reads the "
-                              "misspelt opt.stereonet_intput_scale, and monodepth_leftright_loss overwrites its own outputs "
-                              "argument: SURVEY.md 0.8), so there is no behaviour to reproduce")
+    raise NotImplementedError(LEFTRIGHT_LOSS_MESSAGE)
   if opt.adapt_mode is None:
     raise ValueError("--adapt_mode is required (NONSTOP, VS, ER, VS+ER or NONE)")
   torch.manual_seed(123)

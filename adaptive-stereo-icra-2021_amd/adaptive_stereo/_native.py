@@ -250,6 +250,10 @@ _SIGNATURES = {
   "as_colormap_apply": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_vp, c_vp, c_int, c_int, c_vp,
                                 c_vp]),
   "as_image_to_cv": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_vp, c_vp]),
+  "as_mirror_pair": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp]),
+  "as_flip_w": (c_int, [c_vp, c_i64, c_int, c_int, c_vp, c_vp]),
+  "as_lr_check": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_float, c_float, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+  "as_lr_fill": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp]),
   "as_prof_enable": (c_int, [c_int]),
   "as_prof_reset": (c_int, []),
   "as_prof_read": (c_int, [c_int, _P(c_i64), _P(ctypes.c_double), _P(ctypes.c_double)]),

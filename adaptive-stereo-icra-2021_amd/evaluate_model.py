@@ -7,6 +7,10 @@
                    epe.csv.  The reference's text overlay needs OpenCV and is left out.
   --mode playback  needs a display and OpenCV windows: raises.
   --mode eval      does nothing in the reference; here it prints train.evaluate()'s metrics.
+  --lr_check       (not in the reference; default off, nothing changes without it) predicts both views in one pass and checks them
+                   against each other (adaptive_stereo.consistency).  save: additionally pred_disp_r/*, lr_code_l/0 (uint8: 0
+                   consistent, 1 occluded, 2 mismatch, 3 out of view, 4 bad input) and pred_disp_l_filled/0.  eval: additionally the
+                   metrics over the ground-truth pixels the check keeps, and the share of pixels kept.
 
 Each mode is a function over a dataset-like iterable of {"color_l/0", "color_r/0", "gt_disp_l/0"} samples.
 """
@@ -19,7 +23,7 @@ from torch.utils.data import DataLoader
 
 import adaptive_stereo.utils.path_utils as paths
 from adaptive_stereo.utils.visualization import DisparityPainter
-from train import evaluate, process_batch
+from train import disparity_metrics, evaluate, process_batch
 
 VIDEO_CMAP, VIDEO_VMIN, VIDEO_VMAX = "inferno", 0, 0.6 * 192
 
@@ -31,23 +35,73 @@ def get_save_filename(save_folder, outputs_key, index):
   return os.path.join(folder, "%04d.pt" % index)
 
 
-def save_outputs(feature_net, stereo_net, batches, save_folder, batch_size, opt=None):
+class _BothViews(object):
+  """--lr_check: both views of a batch and their check; the buffers are kept per batch shape (the last batch may be smaller)."""
+
+  def __init__(self, feature_net, stereo_net):
+    if stereo_net.input_scale != 0:
+      raise ValueError("--lr_check: the check runs on pred_disp_{l,r}/0; a StereoNet with input_scale %r has none"
+                       % (stereo_net.input_scale,))
+    self.feature_net, self.stereo_net, self._checkers = feature_net, stereo_net, {}
+
+  def __call__(self, left, right):
+    """-> (outputs with _l and _r keys, LRCheck, the left disparity filled)"""
+    from adaptive_stereo.consistency import LeftRightConsistency, predict_disparity_leftright
+    left, right = left.float().contiguous(), right.float().contiguous()
+    outputs = predict_disparity_leftright(self.feature_net, self.stereo_net, left, right, output_cost_volume=True)
+    B, _, H, W = left.shape
+    if (B, H, W) not in self._checkers:
+      self._checkers[(B, H, W)] = LeftRightConsistency(H, W, batch=B, device=left.device)
+    lrc = self._checkers[(B, H, W)]
+    disp_l = outputs["pred_disp_l/0"].contiguous()
+    chk = lrc.check(disp_l, outputs["pred_disp_r/0"])
+    return outputs, chk, lrc.fill(disp_l, chk.code_l)
+
+
+def save_outputs(feature_net, stereo_net, batches, save_folder, batch_size, opt=None, lr_check=False):
   """batches: an iterable of collated samples (a DataLoader, or a list of dicts of [b,...] tensors).  Returns the number of
   samples written per key."""
   feature_net.eval(); stereo_net.eval()
   written = 0
+  both = _BothViews(feature_net, stereo_net) if lr_check else None
   with torch.no_grad():
     for i, inputs in enumerate(batches):
       left, right = inputs["color_l/0"].cuda(), inputs["color_r/0"].cuda()
-      outputs = process_batch(feature_net, stereo_net, left, right, opt, output_cost_volume=True)
+      if both is not None:
+        outputs, chk, filled = both(left, right)
+        outputs = dict(outputs)
+        outputs["lr_code_l/0"], outputs["pred_disp_l_filled/0"] = chk.code_l, filled
+      else:
+        outputs = process_batch(feature_net, stereo_net, left, right, opt, output_cost_volume=True)
       for key in outputs:
-        if "pred_disp" in key:
+        if "pred_disp" in key or key.startswith("lr_code"):
           for j in range(len(outputs[key])):
             torch.save(outputs[key][j].detach().cpu().clone(), get_save_filename(save_folder, key, batch_size * i + j))
       written += left.shape[0]
       total = " of %d" % len(batches) if hasattr(batches, "__len__") else ""
       print("saved batch %d%s (%d samples)" % (i + 1, total, written), flush=True)
   return written
+
+
+def evaluate_lr_check(feature_net, stereo_net, val_loader):
+  """{"EPE", "D1_all_{2,3,4,5}px"} of train.disparity_metrics over the ground-truth pixels whose left-right code is 0 (the kernel
+  counts gt > 0, so it is handed gt * valid_l), averaged per batch as train.evaluate averages, and "kept": the share of all
+  pixels with code 0."""
+  feature_net.eval(); stereo_net.eval()
+  both = _BothViews(feature_net, stereo_net)
+  rows, kept, pixels = [], [], 0
+  with torch.no_grad():
+    for inputs in val_loader:
+      left, right = inputs["color_l/0"].cuda(), inputs["color_r/0"].cuda()
+      gt = inputs["gt_disp_l/0"].cuda().float()
+      outputs, chk, _ = both(left, right)
+      rows.append(disparity_metrics(outputs["pred_disp_l/0"], gt * chk.valid_l))
+      kept.append(chk.counts[:, 0, 0].sum().clone())               # the buffers are overwritten by the next batch
+      pixels += gt.numel()
+    m = torch.stack(rows).mean(dim=0).cpu() if rows else torch.zeros(5)
+    share = float(torch.stack(kept).sum()) / pixels if pixels else 0.0
+  return {"EPE": float(m[0]), "D1_all_2px": float(m[1]), "D1_all_3px": float(m[2]), "D1_all_4px": float(m[3]),
+          "D1_all_5px": float(m[4]), "kept": share}
 
 
 def frame_epe(pred, gt):
@@ -100,18 +154,22 @@ def main(opt):
   save_folder = os.path.join(opt.load_weights_folder, "outputs", opt.split)
   os.makedirs(save_folder, exist_ok=True)
   dataset = StereoDataset(opt.dataset_path, opt.dataset_name, opt.split, opt.height, opt.width, opt.subsplit, scales=opt.scales,
-                          do_hflip=False, random_crop=False, load_disp_left=True, load_disp_right=False)
+                          do_hflip=False, random_crop=False, load_disp_left=True, load_disp_right=False,
+                          splits_path=opt.splits_path)
+  workers = opt.batch_size if opt.num_workers is None else opt.num_workers
   if opt.mode == "save":
     feature_net, stereo_net = load_networks(opt)
-    loader = DataLoader(dataset, opt.batch_size, False, num_workers=opt.batch_size, pin_memory=True, drop_last=False)
-    save_outputs(feature_net, stereo_net, loader, save_folder, opt.batch_size, opt)
+    loader = DataLoader(dataset, opt.batch_size, False, num_workers=workers, pin_memory=True, drop_last=False)
+    save_outputs(feature_net, stereo_net, loader, save_folder, opt.batch_size, opt, lr_check=opt.lr_check)
   elif opt.mode == "video":
     write_video_frames(dataset, save_folder, paths.output_folder("video"), opt.frames)
   elif opt.mode == "eval":
     feature_net, stereo_net = load_networks(opt)
     opt.stereonet_input_scale = 0
-    loader = DataLoader(dataset, opt.batch_size, False, num_workers=opt.batch_size, pin_memory=True, drop_last=False)
+    loader = DataLoader(dataset, opt.batch_size, False, num_workers=workers, pin_memory=True, drop_last=False)
     print(evaluate(feature_net, stereo_net, loader, opt))
+    if opt.lr_check:
+      print("left-right consistent pixels only:", evaluate_lr_check(feature_net, stereo_net, loader))
   else:
     raise NotImplementedError()
 
@@ -136,6 +194,10 @@ def make_parser():
   p.add_argument("--wait", default=False, action="store_true")
   p.add_argument("--frames", default=-1, type=int, help="stop --mode video after this many frames (-1: all)")
   p.add_argument("--save_disp_as_image", action="store_true", default=False)
+  p.add_argument("--lr_check", action="store_true", default=False,
+                 help="predict both views and check them against each other (save: extra outputs; eval: extra metrics)")
+  p.add_argument("--splits_path", default=None, type=str, help="folder of the split folders (default: the package's splits/)")
+  p.add_argument("--num_workers", default=None, type=int, help="loader processes (default: the batch size, as the reference)")
   return p
 
 

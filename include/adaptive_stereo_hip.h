@@ -995,6 +995,54 @@ int as_colormap_apply(const float* x, const float* y, int B, int H, int W, int a
                       const void* workspace, const void* table, int N, int mode, void* out, void* stream);
 int as_image_to_cv(const float* in, int B, int C, int H, int W, int flip, float div, int out_f32, void* out, void* stream);
 
+/* ---- both-view inference: mirrored batches, left-right consistency check, background fill (csrc/lr_consistency.hip) ----
+ * The reference's predict_disparity_leftright (adapt.py:40-62) runs the network once over [left; flip(right)] and
+ * [right; flip(left)]: the second half of the output is the right view's disparity, mirrored in x.  The check keeps a pixel only
+ * if the pixel it maps to in the other view maps back; the fill replaces the rest from the background.  tests/lr_consistency_ref.py
+ * restates the three contracts below in numpy float32.  All maps are dense fp32 [B][1][H][W] unless stated; every entry point is
+ * stream-ordered, allocates nothing and reads nothing back (capturable).  AS_ERR_ARG, before anything is enqueued, for a NULL
+ * required pointer, a non-positive extent or an extent beyond what the kernel indexes (named in as_last_error).
+ *
+ * as_mirror_pair: one launch.  left, right [B][C][H][W] -> left_batch [2B][C][H][W] = [left ; right mirrored in x],
+ *   right_batch [2B][C][H][W] = [right ; left mirrored in x], "mirrored" being m[b][c][y][x] = v[b][c][y][W-1-x].  Data movement
+ *   only.  Four elements per lane when W % 4 == 0 and all four bases are 16-byte aligned, two when W % 2 == 0 and they are
+ *   8-byte aligned, one otherwise; the outputs may alias neither each other nor an input.
+ * as_flip_w: dst[p][y][x] = src[p][y][W-1-x] over `planes` planes of H x W, out of place (dst != src); the same three routes.
+ *
+ * as_lr_check: one kernel launch (and a memset node when counts is given) for both views.  Every output pointer is optional
+ *   (NULL: not written, not touched), at least one must be given.  mirrored = 1: disp_r is the map as the network produced it for
+ *   the mirrored pair, i.e. element [b][y][W-1-x] holds the right view's pixel x; the kernel indexes it that way and every output
+ *   is in the ordinary (unmirrored) layout, bit-identical to mirrored = 0 on the flipped-back map.  Below, R[x] and L[x] are the
+ *   right and left view's row y of image b in the ordinary layout.  tol_abs, tol_rel: finite, >= 0.  W <= 2^24, B <= 65535.
+ *   The left view at (b, y, x), in fp32, every operation rounded once and none contracted:
+ *     1  d = L[x].  !(d >= 0) or d == +inf: code 4 (bad input).
+ *     2  u = (float)x - d.  u < 0: code 3 (out of view).
+ *     3  i0 = (int)floorf(u), i1 = min(i0 + 1, W - 1), t = u - (float)i0, a = R[i0], b = R[i1].
+ *     4  r = (t == 0) ? a : a + t * (b - a): the subtraction, the product and the sum each rounded once.  With t == 0 the
+ *        neighbour b does not enter, so a NaN there does not reach r.
+ *     5  r not finite, or r < 0: code 4.
+ *     6  e = fabsf(d - r), tol = fmaxf(tol_abs, tol_rel * d).
+ *     7  code 0 (consistent) if e <= tol; else 1 (occluded) if r > d: something nearer covers the pixel; else 2 (mismatch).
+ *   The right view at (b, y, x) is the mirror statement: d = R[x]; u = (float)x + d; out of view if u > (float)(W - 1); a and b
+ *   are taken from L.
+ *   code_l, code_r: uint8.  valid_l, valid_r: fp32, 1.0 where the code is 0 and 0.0 elsewhere (the `confidence` map of
+ *   as_disp_to_points_gated as it is).  diff_l, diff_r: fp32 e, the quiet NaN 0x7FC00000 where the code is 3 or 4.
+ *   counts: int32 [B][2][5] (image, view 0 = left / 1 = right, code), 4-byte aligned, OVERWRITTEN by the call: cleared by a memset
+ *   node, then integer adds only, so exact and independent of the order.  H * W <= 2^31 - 1.
+ *
+ * as_lr_fill: per row of disp [B][1][H][W] with code uint8 [B][1][H][W]: out = disp where the code is 0; elsewhere, with l the
+ *   value of the nearest code-0 pixel to the left in the row and r that of the nearest one to the right, out = (r < l) ? r : l
+ *   when both exist (the smaller is the background), the existing one when only one does, and 0.0 ("no measurement") when the
+ *   row holds no code-0 pixel.  Selection only.  out may not alias disp.  One workgroup per row; a pass covers 1024 pixels, a
+ *   longer row is carried from pass to pass. */
+int as_mirror_pair(const float* left, const float* right, int B, int C, int H, int W, float* left_batch, float* right_batch,
+                   void* stream);
+int as_flip_w(const float* src, int64_t planes, int H, int W, float* dst, void* stream);
+int as_lr_check(const float* disp_l, const float* disp_r, int mirrored, int B, int H, int W, float tol_abs, float tol_rel,
+                uint8_t* code_l, uint8_t* code_r, float* valid_l, float* valid_r, float* diff_l, float* diff_r, int32_t* counts,
+                void* stream);
+int as_lr_fill(const float* disp, const uint8_t* code, int B, int H, int W, float* out, void* stream);
+
 /* ---- measurement hook (bench.py roofline leg) -----------------------------------
  * When enabled, as_conv32_fwd and as_conv32_wgrad bracket their main kernel with HIP events on the
  * launch stream and account its algorithmic FLOPs (2 * voxels * 32 * 32 * taps).  Kernel ids:

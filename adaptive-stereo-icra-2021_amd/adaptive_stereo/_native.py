@@ -254,6 +254,8 @@ _SIGNATURES = {
   "as_flip_w": (c_int, [c_vp, c_i64, c_int, c_int, c_vp, c_vp]),
   "as_lr_check": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_float, c_float, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
   "as_lr_fill": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp]),
+  "as_disp_edge_check": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_float, c_float, c_vp, c_vp, c_vp, c_vp, c_vp]),
+  "as_disp_speckle": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_float, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
   "as_prof_enable": (c_int, [c_int]),
   "as_prof_reset": (c_int, []),
   "as_prof_read": (c_int, [c_int, _P(c_i64), _P(ctypes.c_double), _P(ctypes.c_double)]),

@@ -194,7 +194,8 @@ class BothViewInference(object):
       return self._graph_result
     return self._eager(left, right)
 
-  def _eager(self, left, right):
+  def _forward_and_check(self, left, right):
+    """-> (disp_l, the right view's disparity still mirrored, LRCheck); disp_filter.FilteredBothViewInference shares it"""
     if self.feature_net.training or self.stereo_net.training:
       raise RuntimeError("BothViewInference: inference only; call .eval() on both networks")
     B = self.lrc.B
@@ -206,7 +207,10 @@ class BothViewInference(object):
     finally:
       self.plan.end()
     disp_l, mirrored_r = disp[:B], disp[B:]
-    chk = self.lrc.check(disp_l, mirrored_r, mirrored=True)
+    return disp_l, mirrored_r, self.lrc.check(disp_l, mirrored_r, mirrored=True)
+
+  def _eager(self, left, right):
+    disp_l, mirrored_r, chk = self._forward_and_check(left, right)
     flip_w(mirrored_r, out=self._disp_r)
     return disp_l, self._disp_r, chk, self.lrc.fill(disp_l, chk.code_l)
 

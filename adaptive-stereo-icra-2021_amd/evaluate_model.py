@@ -11,6 +11,11 @@
                    against each other (adaptive_stereo.consistency).  save: additionally pred_disp_r/*, lr_code_l/0 (uint8: 0
                    consistent, 1 occluded, 2 mismatch, 3 out of view, 4 bad input) and pred_disp_l_filled/0.  eval: additionally the
                    metrics over the ground-truth pixels the check keeps, and the share of pixels kept.
+  --post_filter    (not in the reference; default off, nothing changes without it) runs the discontinuity check and the speckle
+                   filter on the left disparity (adaptive_stereo.disp_filter; --edge_tol, --speckle_diff, --speckle_size), alone
+                   or on what --lr_check kept.  save: additionally filter_code_l/0 (uint8: the codes above, 5 discontinuity,
+                   6 speckle), and with --lr_check pred_disp_l_filled/0 is filled from the combined code.  eval: additionally
+                   the metrics over the ground-truth pixels the filter keeps, and the share of pixels kept.
 
 Each mode is a function over a dataset-like iterable of {"color_l/0", "color_r/0", "gt_disp_l/0"} samples.
 """
@@ -46,21 +51,42 @@ class _BothViews(object):
 
   def __call__(self, left, right):
     """-> (outputs with _l and _r keys, LRCheck, the left disparity filled)"""
-    from adaptive_stereo.consistency import LeftRightConsistency, predict_disparity_leftright
+    from adaptive_stereo.consistency import predict_disparity_leftright
     left, right = left.float().contiguous(), right.float().contiguous()
     outputs = predict_disparity_leftright(self.feature_net, self.stereo_net, left, right, output_cost_volume=True)
-    B, _, H, W = left.shape
-    if (B, H, W) not in self._checkers:
-      self._checkers[(B, H, W)] = LeftRightConsistency(H, W, batch=B, device=left.device)
-    lrc = self._checkers[(B, H, W)]
     disp_l = outputs["pred_disp_l/0"].contiguous()
+    lrc = self.checker(disp_l)
     chk = lrc.check(disp_l, outputs["pred_disp_r/0"])
     return outputs, chk, lrc.fill(disp_l, chk.code_l)
 
+  def checker(self, disp):
+    """the LeftRightConsistency of a batch of maps [B,1,H,W]"""
+    from adaptive_stereo.consistency import LeftRightConsistency
+    B, _, H, W = disp.shape
+    if (B, H, W) not in self._checkers:
+      self._checkers[(B, H, W)] = LeftRightConsistency(H, W, batch=B, device=disp.device)
+    return self._checkers[(B, H, W)]
 
-def save_outputs(feature_net, stereo_net, batches, save_folder, batch_size, opt=None, lr_check=False):
+
+class _PostFilter(object):
+  """--post_filter: the DisparityFilter of a batch shape (the last batch may be smaller), with the flags' thresholds."""
+
+  def __init__(self, opt):
+    self.edge_tol, self.max_diff, self.max_size, self._filters = opt.edge_tol, opt.speckle_diff, opt.speckle_size, {}
+
+  def __call__(self, disp, code_in=None):
+    """-> DispFilter of the left disparity [B,1,H,W], on what code_in (the left-right check's code_l, or None) kept"""
+    from adaptive_stereo.disp_filter import DisparityFilter
+    key = tuple(disp.shape)
+    if key not in self._filters:
+      self._filters[key] = DisparityFilter(key[2], key[3], batch=key[0], tol_abs=self.edge_tol, max_diff=self.max_diff,
+                                           max_size=self.max_size, device=disp.device)
+    return self._filters[key](disp, code_in)
+
+
+def save_outputs(feature_net, stereo_net, batches, save_folder, batch_size, opt=None, lr_check=False, post_filter=None):
   """batches: an iterable of collated samples (a DataLoader, or a list of dicts of [b,...] tensors).  Returns the number of
-  samples written per key."""
+  samples written per key.  post_filter: a _PostFilter, or None."""
   feature_net.eval(); stereo_net.eval()
   written = 0
   both = _BothViews(feature_net, stereo_net) if lr_check else None
@@ -73,8 +99,15 @@ def save_outputs(feature_net, stereo_net, batches, save_folder, batch_size, opt=
         outputs["lr_code_l/0"], outputs["pred_disp_l_filled/0"] = chk.code_l, filled
       else:
         outputs = process_batch(feature_net, stereo_net, left, right, opt, output_cost_volume=True)
+      if post_filter is not None:
+        outputs = dict(outputs)
+        disp_l = outputs["pred_disp_l/0"].float().contiguous()
+        filt = post_filter(disp_l, chk.code_l if both is not None else None)
+        outputs["filter_code_l/0"] = filt.code
+        if both is not None:                                         # the fill from the combined code, into a buffer of its own
+          outputs["pred_disp_l_filled/0"] = both.checker(disp_l).fill(disp_l, filt.code, out=torch.empty_like(disp_l))
       for key in outputs:
-        if "pred_disp" in key or key.startswith("lr_code"):
+        if "pred_disp" in key or key.startswith("lr_code") or key.startswith("filter_code"):
           for j in range(len(outputs[key])):
             torch.save(outputs[key][j].detach().cpu().clone(), get_save_filename(save_folder, key, batch_size * i + j))
       written += left.shape[0]
@@ -97,6 +130,32 @@ def evaluate_lr_check(feature_net, stereo_net, val_loader):
       outputs, chk, _ = both(left, right)
       rows.append(disparity_metrics(outputs["pred_disp_l/0"], gt * chk.valid_l))
       kept.append(chk.counts[:, 0, 0].sum().clone())               # the buffers are overwritten by the next batch
+      pixels += gt.numel()
+    m = torch.stack(rows).mean(dim=0).cpu() if rows else torch.zeros(5)
+    share = float(torch.stack(kept).sum()) / pixels if pixels else 0.0
+  return {"EPE": float(m[0]), "D1_all_2px": float(m[1]), "D1_all_3px": float(m[2]), "D1_all_4px": float(m[3]),
+          "D1_all_5px": float(m[4]), "kept": share}
+
+
+def evaluate_post_filter(feature_net, stereo_net, val_loader, opt, lr_check=False):
+  """evaluate_lr_check's figures over the ground-truth pixels the post-filter keeps (code 0 after the edge check and the speckle
+  pass; with lr_check on what the left-right check kept): {"EPE", "D1_all_{2,3,4,5}px", "kept"}."""
+  feature_net.eval(); stereo_net.eval()
+  both = _BothViews(feature_net, stereo_net) if lr_check else None
+  post = _PostFilter(opt)
+  rows, kept, pixels = [], [], 0
+  with torch.no_grad():
+    for inputs in val_loader:
+      left, right = inputs["color_l/0"].cuda(), inputs["color_r/0"].cuda()
+      gt = inputs["gt_disp_l/0"].cuda().float()
+      if both is not None:
+        outputs, chk, _ = both(left, right)
+      else:
+        outputs, chk = process_batch(feature_net, stereo_net, left, right, opt), None
+      disp_l = outputs["pred_disp_l/0"].float().contiguous()
+      filt = post(disp_l, chk.code_l if chk is not None else None)
+      rows.append(disparity_metrics(disp_l, gt * filt.valid))
+      kept.append(filt.counts[:, 0].sum().clone())                   # the buffers are overwritten by the next batch
       pixels += gt.numel()
     m = torch.stack(rows).mean(dim=0).cpu() if rows else torch.zeros(5)
     share = float(torch.stack(kept).sum()) / pixels if pixels else 0.0
@@ -160,7 +219,8 @@ def main(opt):
   if opt.mode == "save":
     feature_net, stereo_net = load_networks(opt)
     loader = DataLoader(dataset, opt.batch_size, False, num_workers=workers, pin_memory=True, drop_last=False)
-    save_outputs(feature_net, stereo_net, loader, save_folder, opt.batch_size, opt, lr_check=opt.lr_check)
+    save_outputs(feature_net, stereo_net, loader, save_folder, opt.batch_size, opt, lr_check=opt.lr_check,
+                 post_filter=_PostFilter(opt) if opt.post_filter else None)
   elif opt.mode == "video":
     write_video_frames(dataset, save_folder, paths.output_folder("video"), opt.frames)
   elif opt.mode == "eval":
@@ -170,6 +230,9 @@ def main(opt):
     print(evaluate(feature_net, stereo_net, loader, opt))
     if opt.lr_check:
       print("left-right consistent pixels only:", evaluate_lr_check(feature_net, stereo_net, loader))
+    if opt.post_filter:
+      print("pixels the post-filter keeps%s:" % (" after the left-right check" if opt.lr_check else ""),
+            evaluate_post_filter(feature_net, stereo_net, loader, opt, lr_check=opt.lr_check))
   else:
     raise NotImplementedError()
 
@@ -196,6 +259,12 @@ def make_parser():
   p.add_argument("--save_disp_as_image", action="store_true", default=False)
   p.add_argument("--lr_check", action="store_true", default=False,
                  help="predict both views and check them against each other (save: extra outputs; eval: extra metrics)")
+  p.add_argument("--post_filter", action="store_true", default=False,
+                 help="discontinuity check and speckle filter of the left disparity (save: extra output; eval: extra metrics)")
+  p.add_argument("--edge_tol", type=float, default=1.0, help="--post_filter: a jump above this many pixels of disparity is an edge")
+  p.add_argument("--speckle_size", type=int, default=200, help="--post_filter: components of at most this many pixels are speckles")
+  p.add_argument("--speckle_diff", type=float, default=1.0,
+                 help="--post_filter: neighbours at most this far apart in disparity belong to one component")
   p.add_argument("--splits_path", default=None, type=str, help="folder of the split folders (default: the package's splits/)")
   p.add_argument("--num_workers", default=None, type=int, help="loader processes (default: the batch size, as the reference)")
   return p

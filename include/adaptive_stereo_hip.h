@@ -1043,6 +1043,43 @@ int as_lr_check(const float* disp_l, const float* disp_r, int mirrored, int B, i
                 void* stream);
 int as_lr_fill(const float* disp, const uint8_t* code, int B, int H, int W, float* out, void* stream);
 
+/* ---- disparity post-filter: discontinuity (flying-pixel) check and speckle removal (csrc/disp_filter.hip) ----
+ * The two steps a classical pipeline runs on a disparity map before it becomes a point cloud; the reference has neither.
+ * tests/disp_filter_ref.py restates both contracts in numpy float32.  Conventions as in the block above: dense fp32
+ * [B][1][H][W] maps, uint8 codes of the same shape, stream-ordered, nothing allocated, nothing read back (capturable).
+ * AS_ERR_ARG before anything is enqueued: a NULL required pointer, a non-positive extent, H * W > 2^31 - 1, B > 65535, a NaN or
+ * negative tolerance (+inf is a tolerance), an output that shares a byte with an input or with another output.
+ * Codes extend those of as_lr_check: 0 keep, 1-3 as the check defines them, 4 bad input, 5 discontinuity, 6 speckle; as_lr_fill
+ * treats every non-zero code as "fill me", so the new ones feed it unchanged.
+ * A pixel is USABLE when code_in is NULL or 0 there and its disparity d has d >= 0 and d != +inf (as_lr_check's step 1; -0.0 is
+ * usable, a NaN is not).  code_in (optional) is the code map of an earlier stage, e.g. as_lr_check's code_l.
+ * counts (optional): int32 [B][7], 4-byte aligned, OVERWRITTEN: cleared by a memset node, then integer adds only; a code above 6
+ * passed through from code_in is written to `code` and counted nowhere.  valid: fp32 1.0 where the code is 0, 0.0 elsewhere.
+ *
+ * as_disp_edge_check: one kernel launch (and the memset node).  code, valid, jump, counts are each optional, one is required.
+ *   At pixel p with d = disp[p], every fp32 operation rounded once and none contracted:
+ *     1  code_in[p] != 0: the code passes through.
+ *     2  p not usable otherwise: code 4.
+ *     3  tol = fmaxf(tol_abs, tol_rel * d) (a NaN product, inf * 0, leaves tol_abs).  Over the 4-neighbours q (left, right, up,
+ *        down) that lie in the image and are usable, e_q = fabsf(d - disp[q]).  Code 5 if any e_q > tol, else 0.  A neighbour
+ *        that is not usable is skipped: a pixel beside a hole is not punished for it.  No usable neighbour: code 0.
+ *   jump: fp32, the largest e_q, 0.0 without a usable neighbour, the quiet NaN 0x7FC00000 for steps 1 and 2.
+ *
+ * as_disp_speckle: connected components of the usable pixels and the rejection of the small ones; four kernel launches (three
+ *   when H == 1) and the memset node.  Two usable 4-neighbours p, q of one image are JOINED iff
+ *   fabsf(disp[p] - disp[q]) <= max_diff: one subtraction, the same bits from either side.  max_diff >= 0, +inf joins every usable
+ *   pair; 0 <= max_size <= 2^31 - 1, and max_size = 0 rejects nothing.
+ *   label (required): int32, the smallest linear index y * W + x of the pixel's component in its image, -1 where not usable.
+ *   size  (required): int32, the component's pixel count, 0 where not usable.
+ *   code  (optional): code_in where that is non-zero; 4 where the pixel is otherwise not usable; 6 where size <= max_size; else 0.
+ *   label and size are also the working arrays (parent links, root counters); every call initialises them itself, so a replay
+ *   needs no clear.  The result is a pure function of the input, bit-identical from run to run.  The kernels work on tiles of
+ *   4 rows x 256 columns, a wave on 64 consecutive pixels of a row. */
+int as_disp_edge_check(const float* disp, const uint8_t* code_in, int B, int H, int W, float tol_abs, float tol_rel, uint8_t* code,
+                       float* valid, float* jump, int32_t* counts, void* stream);
+int as_disp_speckle(const float* disp, const uint8_t* code_in, int B, int H, int W, float max_diff, int max_size, int32_t* label,
+                    int32_t* size, uint8_t* code, float* valid, int32_t* counts, void* stream);
+
 /* ---- measurement hook (bench.py roofline leg) -----------------------------------
  * When enabled, as_conv32_fwd and as_conv32_wgrad bracket their main kernel with HIP events on the
  * launch stream and account its algorithmic FLOPs (2 * voxels * 32 * 32 * taps).  Kernel ids:

@@ -57,6 +57,11 @@ class DepthCamera(ctypes.Structure):
   _fields_ = [(n, c_float) for n in ("fb", "fxs", "fys", "cxs", "cys", "max_depth", "depth_scale", "depth_trunc")]
 
 
+class RectifyCamera(ctypes.Structure):
+  """as_rectify_camera: fp32 of inv(K_new * R_rect), the raw camera's matrix and its distortion coefficients in OpenCV's order."""
+  _fields_ = [("m", c_float * 9)] + [(n, c_float) for n in ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3", "k4", "k5", "k6")]
+
+
 _P = ctypes.POINTER
 _SIGNATURES = {
   # name: (restype, [argtypes])
@@ -256,6 +261,9 @@ _SIGNATURES = {
   "as_lr_fill": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp]),
   "as_disp_edge_check": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_float, c_float, c_vp, c_vp, c_vp, c_vp, c_vp]),
   "as_disp_speckle": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_float, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+  "as_rectify_map": (c_int, [_P(RectifyCamera), c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
+  "as_rectify_pair": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, _P(RectifyCamera), _P(RectifyCamera), c_int, c_int, c_int, c_int,
+                              c_float, c_vp, c_vp, c_vp]),
   "as_prof_enable": (c_int, [c_int]),
   "as_prof_reset": (c_int, []),
   "as_prof_read": (c_int, [c_int, _P(c_i64), _P(ctypes.c_double), _P(ctypes.c_double)]),

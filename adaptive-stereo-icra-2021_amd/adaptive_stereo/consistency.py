@@ -229,3 +229,9 @@ class BothViewInference(object):
   def inputs(self):
     """The static inputs (left, right) of the captured graph: a caller that fills them itself saves the copy."""
     return self._left, self._right
+
+  @torch.no_grad()
+  def run_static(self):
+    """The chain, eagerly, on the static inputs as they stand: for a stage in front that fills inputs() itself and records the
+    whole sequence in a capture of its own (rectify.RectifiedInference)."""
+    return self._eager(self._left, self._right)

@@ -20,6 +20,8 @@ void as_wgrad_reduce_enqueue(hipStream_t st, const float* partial, const float* 
 // *cursor += B (saturating); either pointer may be NULL.  1 <= B <= AS_CURSOR_MAX_BATCH keeps cursor + b inside int32.
 #define AS_CURSOR_MAX_BATCH 65535
 void as_cursor_advance_enqueue(hipStream_t st, int32_t* cursor, int32_t* dropped, int B, int capacity);
+// p[0 .. n) = 0 by a kernel launch (cursor.hip): the clear of per-call counters that stays right in every replay of a captured graph
+void as_zero_i32_enqueue(hipStream_t st, int32_t* p, int n);
 // measurement hook (optim.hip): event pair around a kernel launch; no-ops unless enabled
 void as_prof_mark(int kernel_id, hipStream_t st, int begin, double flops);
 // kernel ids of the measurement hook (bench.py reads them back with as_prof_read); the `flops` argument carries FLOPs for

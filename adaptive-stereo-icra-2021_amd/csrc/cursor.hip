@@ -18,3 +18,15 @@ __global__ void cursor_advance_kernel(int32_t* cursor, int32_t* dropped, int B, 
 void as_cursor_advance_enqueue(hipStream_t st, int32_t* cursor, int32_t* dropped, int B, int capacity) {
   hipLaunchKernelGGL(cursor_advance_kernel, dim3(1), dim3(1), 0, st, cursor, dropped, B, capacity);
 }
+
+// Counters cleared by a KERNEL node, not by hipMemsetAsync: a memset node of a captured graph was seen (ROCm 7.2, MI355X) to fill
+// with a stale 16-byte pattern from its second replay on (the counters then came out as that pattern plus the counts), the first
+// replay and every eager call being right.  A kernel's arguments are part of its node.
+__global__ void zero_i32_kernel(int32_t* p, int n) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) p[i] = 0;
+}
+
+void as_zero_i32_enqueue(hipStream_t st, int32_t* p, int n) {
+  hipLaunchKernelGGL(zero_i32_kernel, dim3(as_div_up(n, 256)), dim3(256), 0, st, p, n);
+}

@@ -11,7 +11,7 @@
 //   disp_edge_kernel      a pixel's own disparity and its four neighbours' (the neighbouring lanes' and rows' loads, out of the
 //                         cache); max |d - d_q| over the usable neighbours against max(tol_abs, tol_rel * d).  The seven counts as
 //                         lr_check_kernel keeps them: per lane, summed over the wave, LDS integers, one global integer atomic per
-//                         code and workgroup onto counts the entry point has zeroed with a memset node.
+//                         code and workgroup onto counts the entry point has zeroed with a small launch (as_zero_i32_enqueue).
 //
 // The speckle filter is connected-component labelling by union-find over the pixel index, label[] being the parent links and
 // size[] the root counters (no further workspace).  A parent is never larger than its pixel, a union links the larger root under
@@ -101,11 +101,8 @@ static __device__ inline void df_add_counts(const int (&mine)[DF_CODES], int* s_
 
 static int df_clear_counts(const char* who, int32_t* counts, int B, hipStream_t st) {
   if (counts == nullptr) return AS_OK;
-  hipError_t e = hipMemsetAsync(counts, 0, (size_t)B * DF_CODES * sizeof(int32_t), st);
-  if (e != hipSuccess) {
-    as_set_error("%s: clearing counts failed: %s", who, hipGetErrorString(e));
-    return AS_ERR_LAUNCH;
-  }
+  as_zero_i32_enqueue(st, counts, B * DF_CODES);
+  AS_CHECK_LAUNCH(who);
   return AS_OK;
 }
 

@@ -16,7 +16,7 @@
 //                            a gather of two neighbours out of the other view's row, which the neighbouring workgroups stream
 //                            through the cache.  The five counts are kept per lane, summed over the wave, added to LDS integers
 //                            and end as one global integer atomic per code and workgroup onto counts the entry point has zeroed
-//                            with a memset node: exact in any order.  The counters of a batch share one or two cache lines,
+//                            with a small launch (as_zero_i32_enqueue): exact in any order.  The counters of a batch share one or two cache lines,
 //                            where atomics serialise, so the workgroups are kept to about 2048 instead of one per tile.
 //   lr_fill_kernel           one workgroup of 256 lanes per row, FILL_ITEMS pixels per lane, so a pass covers FILL_SPAN = 1024
 //                            pixels.  "The last code-0 value so far" is an associative operator (the right operand wins when it
@@ -230,11 +230,8 @@ extern "C" int as_lr_check(const float* disp_l, const float* disp_r, int mirrore
   AS_CHECK_ARG(!counts || ((uintptr_t)counts & 3) == 0, "as_lr_check: counts must be 4-byte aligned");
   hipStream_t st = (hipStream_t)stream;
   if (counts) {
-    hipError_t e = hipMemsetAsync(counts, 0, (size_t)B * 2 * LR_CODES * sizeof(int32_t), st);
-    if (e != hipSuccess) {
-      as_set_error("as_lr_check: clearing counts failed: %s", hipGetErrorString(e));
-      return AS_ERR_LAUNCH;
-    }
+    as_zero_i32_enqueue(st, counts, B * 2 * LR_CODES);
+    AS_CHECK_LAUNCH("as_lr_check");
   }
   LrCheckArgs a;
   a.disp[0] = disp_l; a.disp[1] = disp_r;

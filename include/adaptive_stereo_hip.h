@@ -1009,7 +1009,8 @@ int as_image_to_cv(const float* in, int B, int C, int H, int W, int flip, float 
  *   8-byte aligned, one otherwise; the outputs may alias neither each other nor an input.
  * as_flip_w: dst[p][y][x] = src[p][y][W-1-x] over `planes` planes of H x W, out of place (dst != src); the same three routes.
  *
- * as_lr_check: one kernel launch (and a memset node when counts is given) for both views.  Every output pointer is optional
+ * as_lr_check: one kernel launch (and a small clearing launch when counts is given: a kernel, because a memset node was seen to
+ *   fill with a stale pattern from the second replay of a captured graph on) for both views.  Every output pointer is optional
  *   (NULL: not written, not touched), at least one must be given.  mirrored = 1: disp_r is the map as the network produced it for
  *   the mirrored pair, i.e. element [b][y][W-1-x] holds the right view's pixel x; the kernel indexes it that way and every output
  *   is in the ordinary (unmirrored) layout, bit-identical to mirrored = 0 on the flipped-back map.  Below, R[x] and L[x] are the
@@ -1053,10 +1054,10 @@ int as_lr_fill(const float* disp, const uint8_t* code, int B, int H, int W, floa
  * treats every non-zero code as "fill me", so the new ones feed it unchanged.
  * A pixel is USABLE when code_in is NULL or 0 there and its disparity d has d >= 0 and d != +inf (as_lr_check's step 1; -0.0 is
  * usable, a NaN is not).  code_in (optional) is the code map of an earlier stage, e.g. as_lr_check's code_l.
- * counts (optional): int32 [B][7], 4-byte aligned, OVERWRITTEN: cleared by a memset node, then integer adds only; a code above 6
+ * counts (optional): int32 [B][7], 4-byte aligned, OVERWRITTEN: cleared by a small launch, then integer adds only; a code above 6
  * passed through from code_in is written to `code` and counted nowhere.  valid: fp32 1.0 where the code is 0, 0.0 elsewhere.
  *
- * as_disp_edge_check: one kernel launch (and the memset node).  code, valid, jump, counts are each optional, one is required.
+ * as_disp_edge_check: one kernel launch (and the clearing launch).  code, valid, jump, counts are each optional, one is required.
  *   At pixel p with d = disp[p], every fp32 operation rounded once and none contracted:
  *     1  code_in[p] != 0: the code passes through.
  *     2  p not usable otherwise: code 4.
@@ -1066,7 +1067,7 @@ int as_lr_fill(const float* disp, const uint8_t* code, int B, int H, int W, floa
  *   jump: fp32, the largest e_q, 0.0 without a usable neighbour, the quiet NaN 0x7FC00000 for steps 1 and 2.
  *
  * as_disp_speckle: connected components of the usable pixels and the rejection of the small ones; four kernel launches (three
- *   when H == 1) and the memset node.  Two usable 4-neighbours p, q of one image are JOINED iff
+ *   when H == 1) and the clearing launch.  Two usable 4-neighbours p, q of one image are JOINED iff
  *   fabsf(disp[p] - disp[q]) <= max_diff: one subtraction, the same bits from either side.  max_diff >= 0, +inf joins every usable
  *   pair; 0 <= max_size <= 2^31 - 1, and max_size = 0 rejects nothing.
  *   label (required): int32, the smallest linear index y * W + x of the pixel's component in its image, -1 where not usable.
@@ -1079,6 +1080,56 @@ int as_disp_edge_check(const float* disp, const uint8_t* code_in, int B, int H, 
                        float* valid, float* jump, int32_t* counts, void* stream);
 int as_disp_speckle(const float* disp, const uint8_t* code_in, int B, int H, int W, float max_diff, int max_size, int32_t* label,
                     int32_t* size, uint8_t* code, float* valid, int32_t* counts, void* stream);
+
+/* ---- stereo rectification of raw camera pairs (csrc/rectify.hip) ----
+ * The stage in front of the network for a rig, or a data set, whose images are NOT rectified: undistortion and the rectifying
+ * rotation as one bilinear gather per output pixel, what a host pipeline does with cv2.initUndistortRectifyMap + cv2.remap.
+ * tests/rectify_ref.py restates the contract in numpy float32.  Stream-ordered, nothing allocated, nothing read back (capturable);
+ * the camera structs are HOST pointers read at call time, as as_depth_camera is.
+ * AS_ERR_ARG before anything is enqueued: a NULL required pointer, a non-positive extent, C outside {1, 3}, 2 * B > 65535,
+ * |i0| or |j0| above 2^30, H * W or H0 * W0 of 2^30 or more, more than 4 * 65535 rows, an output that is not 4-byte aligned.
+ *
+ * as_rectify_camera: m is inv(K_new[:3,:3] * R_rect) rounded to fp32 ONCE, after an fp64 inversion on the host (row-major): it
+ * takes a rectified pixel (u, v, 1) to a ray in the raw camera's frame.  fx, fy, cx, cy are the RAW camera's matrix, k1 .. k6,
+ * p1, p2 its distortion coefficients in OpenCV's order (k1, k2, p1, p2, k3, k4, k5, k6); absent ones are 0.
+ *
+ * (i0, j0, H, W) is the window of the rectified image that is produced; any window, also one that leaves what the raw image
+ * covers.  At output pixel (y, x), x in [0, W), y in [0, H), every line single IEEE fp32 operations in the written order, none
+ * contracted, every division correctly rounded:
+ *     u = (float)(x + j0), v = (float)(y + i0)
+ *     X = (m0*u + m1*v) + m2;  Y = (m3*u + m4*v) + m5;  Z = (m6*u + m7*v) + m8
+ *     xn = X / Z;  yn = Y / Z;  xx = xn*xn;  yy = yn*yn;  xy = xn*yn;  r2 = xx + yy
+ *     num = ((k3*r2 + k2)*r2 + k1)*r2 + 1.f;  den = ((k6*r2 + k5)*r2 + k4)*r2 + 1.f;  rad = num / den
+ *     xd = (xn*rad + (2.f*p1)*xy) + p2*(r2 + 2.f*xx)
+ *     yd = (yn*rad + p1*(r2 + 2.f*yy)) + (2.f*p2)*xy
+ *     us = fx*xd + cx;  vs = fy*yd + cy
+ *     valid = Z > 0 && us >= 0 && us <= (float)(W0-1) && vs >= 0 && vs <= (float)(H0-1)          (a NaN fails)
+ *   and, for a valid pixel only (the coordinates of an invalid one may be NaN, infinite or beyond int32):
+ *     x0 = (int)floorf(us); x1 = min(x0+1, W0-1); ax = us - (float)x0;  y0, y1, ay likewise
+ *     per channel, as float: a, b = row y0 at x0, x1;  c, d = row y1 at x0, x1
+ *     top = (b-a)*ax + a;  bot = (d-c)*ax + c;  val = (bot-top)*ay + top;  out = val / 255.f
+ *   an invalid pixel is `fill` in every plane.
+ * Validity depends on the calibration and the window only, never on the image: the per-frame call writes no mask.
+ * Not modelled: fisheye lenses; and, as in OpenCV, the forward polynomial is evaluated wherever the ray points, so far outside the
+ * field of view a strongly negative radial term folds back into the image (valid, with content from elsewhere).
+ *
+ * as_rectify_map: one launch.  map_x, map_y (us, vs as computed, NaN included) and valid (1.0f / 0.0f) are each [H][W] fp32 and
+ *   each optional; one is required.  Called once when a rectifier is built.
+ * as_rectify_pair: one launch for both cameras and the whole batch.  src_l, src_r: [B][H0][W0][C] uint8, C in {1, 3} (the
+ *   layout as_decode_rgb8 takes, and mono cameras); dst_l, dst_r: [B][3][H][W] fp32 (C = 1 writes one value to all three planes).
+ *   The coordinates are recomputed by the same device function as_rectify_map runs, so its map is exactly what was sampled.
+ *   A workgroup covers 4 rows x 256 columns, a lane pixels lane, lane + 64, lane + 128 and lane + 192 of them: one route for
+ *   every width and alignment (the outputs need 4-byte alignment only). */
+typedef struct as_rectify_camera {
+  float m[9];
+  float fx, fy, cx, cy;
+  float k1, k2, p1, p2, k3, k4, k5, k6;
+} as_rectify_camera;
+int as_rectify_map(const as_rectify_camera* cam, int H0, int W0, int i0, int j0, int H, int W, float* map_x, float* map_y,
+                   float* valid, void* stream);
+int as_rectify_pair(const uint8_t* src_l, const uint8_t* src_r, int B, int H0, int W0, int C, const as_rectify_camera* cam_l,
+                    const as_rectify_camera* cam_r, int i0, int j0, int H, int W, float fill, float* dst_l, float* dst_r,
+                    void* stream);
 
 /* ---- measurement hook (bench.py roofline leg) -----------------------------------
  * When enabled, as_conv32_fwd and as_conv32_wgrad bracket their main kernel with HIP events on the

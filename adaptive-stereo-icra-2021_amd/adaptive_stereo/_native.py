@@ -264,6 +264,10 @@ _SIGNATURES = {
   "as_rectify_map": (c_int, [_P(RectifyCamera), c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
   "as_rectify_pair": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, _P(RectifyCamera), _P(RectifyCamera), c_int, c_int, c_int, c_int,
                               c_float, c_vp, c_vp, c_vp]),
+  "as_sgm_census": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp]),
+  "as_sgm_workspace": (c_i64, [c_int, c_int, c_int, c_int]),
+  "as_sgm_aggregate": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp]),
+  "as_sgm_select": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_float, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
   "as_prof_enable": (c_int, [c_int]),
   "as_prof_reset": (c_int, []),
   "as_prof_read": (c_int, [c_int, _P(c_i64), _P(ctypes.c_double), _P(ctypes.c_double)]),

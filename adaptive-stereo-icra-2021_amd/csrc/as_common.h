@@ -113,6 +113,23 @@ static inline int as_launch_lds(const void* fn, AsPerDevice& once, int attr_byte
 
 static inline int as_div_up(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
+// Byte ranges of an entry point's arguments (disp_filter.hip, sgm.hip); a NULL pointer overlaps nothing.
+struct AsRange {
+  const void* p;
+  int64_t bytes;
+};
+static inline bool as_overlap(const void* a, int64_t a_bytes, const void* b, int64_t b_bytes) {
+  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+  return a != nullptr && b != nullptr && pa < pb + (uintptr_t)b_bytes && pb < pa + (uintptr_t)a_bytes;
+}
+// no output (r[inputs .. n)) shares a byte with an input or with another output
+static inline bool as_disjoint(const AsRange* r, int inputs, int n) {
+  for (int o = inputs; o < n; ++o)
+    for (int k = 0; k < o; ++k)
+      if (as_overlap(r[o].p, r[o].bytes, r[k].p, r[k].bytes)) return false;
+  return true;
+}
+
 // Wave-level sum over all 64 lanes (result in every lane).
 __device__ inline float wave_sum(float v) {
 #pragma unroll

@@ -63,23 +63,6 @@ static __device__ inline bool df_usable(const uint8_t* __restrict__ cin, long at
   return (cin == nullptr || cin[at] == 0) && d >= 0.f && d != INFINITY;
 }
 
-static inline bool df_overlap(const void* a, int64_t a_bytes, const void* b, int64_t b_bytes) {
-  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-  return a != nullptr && b != nullptr && pa < pb + (uintptr_t)b_bytes && pb < pa + (uintptr_t)a_bytes;
-}
-
-struct DfRange {
-  const void* p;
-  int64_t bytes;
-};
-// no output (r[inputs .. n)) shares a byte with an input or with another output
-static inline bool df_disjoint(const DfRange* r, int inputs, int n) {
-  for (int o = inputs; o < n; ++o)
-    for (int k = 0; k < o; ++k)
-      if (df_overlap(r[o].p, r[o].bytes, r[k].p, r[k].bytes)) return false;
-  return true;
-}
-
 static inline dim3 df_grid(int B, int H, int W) {
   const int64_t tiles = (int64_t)as_div_up(H, DF_ROWS) * as_div_up(W, DF_SPAN);
   const int64_t per_image = as_div_up(DF_GROUPS, B);
@@ -181,8 +164,8 @@ extern "C" int as_disp_edge_check(const float* disp, const uint8_t* code_in, int
   AS_CHECK_ARG(code || valid || jump || counts, "as_disp_edge_check: no output requested");
   AS_CHECK_ARG(!counts || ((uintptr_t)counts & 3) == 0, "as_disp_edge_check: counts must be 4-byte aligned");
   const int64_t n = (int64_t)B * H * W;
-  const DfRange r[] = {{disp, n * 4}, {code_in, n}, {code, n}, {valid, n * 4}, {jump, n * 4}, {counts, (int64_t)B * DF_CODES * 4}};
-  AS_CHECK_ARG(df_disjoint(r, 2, 6), "as_disp_edge_check: an output may alias neither an input nor another output (overlapping ranges)");
+  const AsRange r[] = {{disp, n * 4}, {code_in, n}, {code, n}, {valid, n * 4}, {jump, n * 4}, {counts, (int64_t)B * DF_CODES * 4}};
+  AS_CHECK_ARG(as_disjoint(r, 2, 6), "as_disp_edge_check: an output may alias neither an input nor another output (overlapping ranges)");
   hipStream_t st = (hipStream_t)stream;
   if (int rc = df_clear_counts("as_disp_edge_check", counts, B, st)) return rc;
   DfEdgeArgs a;
@@ -381,9 +364,9 @@ extern "C" int as_disp_speckle(const float* disp, const uint8_t* code_in, int B,
   AS_CHECK_ARG((((uintptr_t)label | (uintptr_t)size | (uintptr_t)counts) & 3) == 0,
                "as_disp_speckle: label, size and counts must be 4-byte aligned");
   const int64_t n = (int64_t)B * H * W;
-  const DfRange r[] = {{disp, n * 4}, {code_in, n}, {label, n * 4}, {size, n * 4}, {code, n}, {valid, n * 4},
+  const AsRange r[] = {{disp, n * 4}, {code_in, n}, {label, n * 4}, {size, n * 4}, {code, n}, {valid, n * 4},
                        {counts, (int64_t)B * DF_CODES * 4}};
-  AS_CHECK_ARG(df_disjoint(r, 2, 7), "as_disp_speckle: an output may alias neither an input nor another output (overlapping ranges)");
+  AS_CHECK_ARG(as_disjoint(r, 2, 7), "as_disp_speckle: an output may alias neither an input nor another output (overlapping ranges)");
   hipStream_t st = (hipStream_t)stream;
   if (int rc = df_clear_counts("as_disp_speckle", counts, B, st)) return rc;
   DfSpeckleArgs a;

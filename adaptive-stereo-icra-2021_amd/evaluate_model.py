@@ -206,16 +206,22 @@ def load_networks(opt):
   return feature_net, stereo_net
 
 
-def main(opt):
-  if opt.mode == "playback":
-    raise RuntimeError("--mode playback opens OpenCV windows and needs a display; use --mode video and view the PNGs")
+def make_dataset(opt):
+  """-> (the evaluation dataset of the flags: no flip, no crop, left ground truth; the loader processes to use).  sgm_baseline.py
+  evaluates on the same samples."""
   from adaptive_stereo.datasets.stereo_dataset import StereoDataset
-  save_folder = os.path.join(opt.load_weights_folder, "outputs", opt.split)
-  os.makedirs(save_folder, exist_ok=True)
   dataset = StereoDataset(opt.dataset_path, opt.dataset_name, opt.split, opt.height, opt.width, opt.subsplit, scales=opt.scales,
                           do_hflip=False, random_crop=False, load_disp_left=True, load_disp_right=False,
                           splits_path=opt.splits_path)
-  workers = opt.batch_size if opt.num_workers is None else opt.num_workers
+  return dataset, opt.batch_size if opt.num_workers is None else opt.num_workers
+
+
+def main(opt):
+  if opt.mode == "playback":
+    raise RuntimeError("--mode playback opens OpenCV windows and needs a display; use --mode video and view the PNGs")
+  save_folder = os.path.join(opt.load_weights_folder, "outputs", opt.split)
+  os.makedirs(save_folder, exist_ok=True)
+  dataset, workers = make_dataset(opt)
   if opt.mode == "save":
     feature_net, stereo_net = load_networks(opt)
     loader = DataLoader(dataset, opt.batch_size, False, num_workers=workers, pin_memory=True, drop_last=False)
@@ -237,21 +243,28 @@ def main(opt):
     raise NotImplementedError()
 
 
+def add_dataset_flags(p):
+  """The flags make_dataset() reads, with the reference's defaults (sgm_baseline.py takes the same ones)."""
+  p.add_argument("--dataset_path", type=str, help="root folder of the dataset")
+  p.add_argument("--dataset_name", type=str, help="dataset loader to use")
+  p.add_argument("--split", type=str, help="folder of split files")
+  p.add_argument("--subsplit", choices=["train", "val", "test"], help="which lines file of the split")
+  p.add_argument("--scales", type=int, nargs="+", default=[0], help="pyramid levels the dataset yields")
+  p.add_argument("--batch_size", type=int, default=8)
+  p.add_argument("--height", type=int, default=512, help="a multiple of 64")
+  p.add_argument("--width", type=int, default=960, help="a multiple of 64")
+  p.add_argument("--splits_path", default=None, type=str, help="folder of the split folders (default: the package's splits/)")
+  p.add_argument("--num_workers", default=None, type=int, help="loader processes (default: the batch size, as the reference)")
+
+
 def make_parser():
   """The reference's flags and defaults; the viewer flags (max_disp_viz, window_sf, wait, save_disp_as_image) are accepted and
   unused, as playback is."""
   p = argparse.ArgumentParser(description="Saved predictions, per-frame images and metrics of a trained StereoNet")
   p.add_argument("--mode", type=str, choices=["save", "playback", "eval", "video"])
-  p.add_argument("--dataset_path", type=str, help="root folder of the dataset")
-  p.add_argument("--dataset_name", type=str, help="dataset loader to use")
-  p.add_argument("--split", type=str, help="folder of split files")
-  p.add_argument("--subsplit", choices=["train", "val", "test"], help="which lines file of the split")
+  add_dataset_flags(p)
   p.add_argument("--load_weights_folder", default=None, type=str, help="folder holding feature_net.pth and stereo_net.pth")
   p.add_argument("--stereonet_k", type=int, default=3, choices=[3, 4], help="the cost volume is built at 1 / 2^k resolution")
-  p.add_argument("--scales", type=int, nargs="+", default=[0], help="pyramid levels the dataset yields")
-  p.add_argument("--batch_size", type=int, default=8)
-  p.add_argument("--height", type=int, default=512, help="a multiple of 64")
-  p.add_argument("--width", type=int, default=960, help="a multiple of 64")
   p.add_argument("--max_disp_viz", type=float, default=300)
   p.add_argument("--window_sf", type=float, default=1.5)
   p.add_argument("--wait", default=False, action="store_true")
@@ -265,8 +278,6 @@ def make_parser():
   p.add_argument("--speckle_size", type=int, default=200, help="--post_filter: components of at most this many pixels are speckles")
   p.add_argument("--speckle_diff", type=float, default=1.0,
                  help="--post_filter: neighbours at most this far apart in disparity belong to one component")
-  p.add_argument("--splits_path", default=None, type=str, help="folder of the split folders (default: the package's splits/)")
-  p.add_argument("--num_workers", default=None, type=int, help="loader processes (default: the batch size, as the reference)")
   return p
 
 

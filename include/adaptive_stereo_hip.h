@@ -1131,6 +1131,60 @@ int as_rectify_pair(const uint8_t* src_l, const uint8_t* src_r, int B, int H0, i
                     const as_rectify_camera* cam_r, int i0, int j0, int H, int W, float fill, float* dst_l, float* dst_r,
                     void* stream);
 
+/* ---- semi-global matching: a network-independent disparity (csrc/sgm.hip) ----
+ * The classical matcher beside the network: census transform, Hamming cost, path aggregation (Hirschmueller 2008), winner
+ * selection for both views out of one volume.  A baseline to score the network against, and sparse proxy labels once the
+ * left-right check and the speckle filter have thinned it.  tests/sgm_ref.py restates the four contracts in numpy; all of it is
+ * integer arithmetic up to the sub-pixel division, so every result is exact and independent of any order.  Conventions as in the
+ * blocks above: dense fp32 [B][C][H][W] images and [B][1][H][W] maps, stream-ordered, nothing allocated, nothing read back
+ * (capturable).  AS_ERR_ARG before anything is enqueued: a NULL required pointer, a non-positive extent, C outside {1, 3},
+ * D outside 1 .. 256, paths outside {4, 8}, P1 < 0, P2 < P1 or P2 > 255, uniqueness outside 0 .. 99, B > 65535,
+ * H * W * D > 2^31 - 1 (H * W > 2^31 - 1 for the census), a census pointer that is not 8-byte aligned, a workspace pointer that
+ * is not 16-byte aligned, an output that shares a byte with an input or with another output.
+ *
+ * as_sgm_census: one launch.  img [B][C][H][W] fp32 -> census uint64 [B][H][W].  Grey value, each fp32 operation rounded once
+ *   and none contracted: C == 3: g = (0.299f * r + 0.587f * g) + 0.114f * b of planes 0, 1, 2; C == 1: the plane itself.
+ *   q = (int)floorf(fminf(fmaxf(g * 255.0f + 0.5f, 0.0f), 255.0f)); a NaN gives 0 through fmaxf.  Window 9 wide x 7 high: for
+ *   dy in -3 .. 3, dx in -4 .. 4, bit k = (dy + 3) * 9 + (dx + 4) is q[clamp(y + dy)][clamp(x + dx)] < q[y][x], coordinates
+ *   clamped to the image.  Bit 31 (the centre) and bit 63 are always 0.  A workgroup covers 8 rows x 32 columns and holds their q
+ *   with the halo in LDS.
+ *
+ * as_sgm_workspace: host function.  Bytes of the aggregation volume S, uint16 [B][H][W][D] with D contiguous, which is all the
+ *   kernels need; 0 on bad arguments.  S begins at the workspace pointer; as_sgm_select reads exactly this layout.
+ *
+ * as_sgm_aggregate: matching cost, never stored: C(y,x,d) = popcount(census_l[y][x] ^ census_r[y][x-d]) for x - d >= 0, and 64
+ *   for x - d < 0 (worse than any real cost).  Path cost for a direction r = (dy, dx), p - r the predecessor of p and
+ *   m = min_k L_r(p-r, k):
+ *     L_r(p,d) = C(p,d) + min( L_r(p-r,d), L_r(p-r,d-1) + P1, L_r(p-r,d+1) + P1, m + P2 ) - m,
+ *   the d-1 and d+1 terms absent at the ends of the range, and L_r(p,d) = C(p,d) when p - r lies outside the image.
+ *   paths = 4: r in (0,+1), (0,-1), (+1,0), (-1,0); paths = 8: those and the four diagonals (+-1,+-1).
+ *   S(p,d) = sum over r of L_r(p,d) <= 8 * (64 + 255) = 2552.  The call initialises S itself: a replay needs no clear.
+ *   Launches: one for the two horizontal paths (it writes S = L(0,+1), then adds L(0,-1) on the way back), then one per remaining
+ *   direction (read-add-write of S): 3 launches at 4 paths, 7 at 8.  A vertical or diagonal line is walked as a column walk: x
+ *   advances by dx per row and wraps modulo W, the recurrence being reset (L = C) at the wrap, so every launch has B * W lines
+ *   of H pixels.  A pixel's D disparities lie four to a lane over the smallest power of two of lanes that holds them; the minimum
+ *   over D is taken across those lanes in registers.
+ *
+ * as_sgm_select: one launch (and the clearing launch when counts is given).  Every output is optional, one is required.
+ *   Left view at (y,x): the column s[d] = S(y,x,d), d in 0 .. n-1 with n = D.  Right view at (y,x): the column
+ *   s[d] = S(y,x+d,d), d in 0 .. n-1 with n = min(D, W - x): the same volume read along its diagonal.
+ *     1  d* = the SMALLEST d attaining the minimum, s1 = s[d*].
+ *     2  not unique iff some k with |k - d*| > 1 has s[k] * (100 - uniqueness) < s1 * 100 (int32; uniqueness 0 rejects nothing).
+ *     3  if 0 < d* < n-1 and den = 2 * (s[d*-1] + s[d*+1] - 2 * s1) > 0 (integers):
+ *        value = (float)d* + (float)(s[d*-1] - s[d*+1]) / (float)den, one correctly rounded division and one sum;
+ *        otherwise value = (float)d*.
+ *     4  code (uint8, extending as_disp_speckle's table by one): 3 out of view, left view only, when d* > x; else 7 not unique;
+ *        else 0.
+ *     5  disp = value where the code is 0, `fill` (passed through bit for bit) elsewhere.
+ *   counts: int32 [B][2][8] (image, view 0 = left / 1 = right, code), 4-byte aligned, OVERWRITTEN: cleared by a small launch,
+ *   then integer adds only. */
+int as_sgm_census(const float* img, int B, int C, int H, int W, uint64_t* census, void* stream);
+int64_t as_sgm_workspace(int B, int H, int W, int D);
+int as_sgm_aggregate(const uint64_t* census_l, const uint64_t* census_r, int B, int H, int W, int D, int P1, int P2, int paths,
+                     void* workspace, void* stream);
+int as_sgm_select(const void* workspace, int B, int H, int W, int D, int uniqueness, float fill, float* disp_l, uint8_t* code_l,
+                  float* disp_r, uint8_t* code_r, int32_t* counts, void* stream);
+
 /* ---- measurement hook (bench.py roofline leg) -----------------------------------
  * When enabled, as_conv32_fwd and as_conv32_wgrad bracket their main kernel with HIP events on the
  * launch stream and account its algorithmic FLOPs (2 * voxels * 32 * 32 * taps).  Kernel ids:

@@ -18,6 +18,61 @@ def check_f32(who, name, t, dims=None, device=None, numel=None):
                           "the GPU" if device is None else device, name, tuple(t.shape), t.dtype, t.device, t.is_contiguous()))
 
 
+def check_shape(who, name, t, shape, device):
+  """After check_f32: `t` has exactly `shape` and lives on `device`."""
+  if tuple(t.shape) != tuple(shape) or t.device != device:
+    raise RuntimeError("%s: %s must be %s on %s (got %s on %s)" % (who, name, tuple(shape), device, tuple(t.shape), t.device))
+
+
+def check_u8(who, name, t, shape, device):
+  """Refuses what is not a contiguous uint8 tensor of exactly `shape` on `device`."""
+  if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or not t.is_contiguous() or tuple(t.shape) != tuple(shape) or \
+     t.device != device:
+    raise RuntimeError("%s: %s must be a contiguous uint8 %s tensor on %s (got %s, %s, %s)"
+                       % (who, name, tuple(shape), device, tuple(getattr(t, "shape", ())), getattr(t, "dtype", None),
+                          getattr(t, "device", None)))
+
+
+def gpu_device(who, device):
+  """torch.device(device), refused unless it is a GPU: what holds device buffers has no CPU path."""
+  dev = torch.device(device)
+  if dev.type != "cuda":
+    raise RuntimeError("adaptive_stereo: %s lives on the GPU (got %s); there is no CPU path" % (who, dev))
+  return dev
+
+
+def int_in(who, name, value, lo, hi):
+  v = int(value)
+  if v != value or not lo <= v <= hi:
+    raise ValueError("%s: %s %r must be an integer in %d .. %d" % (who, name, value, lo, hi))
+  return v
+
+
+class MapOperator(object):
+  """What the operators on maps [batch,1,height,width] with buffers fixed at construction share (LeftRightConsistency,
+  DisparityFilter, SemiGlobalMatcher): the size, the device, the check of an argument against them and the shares of the codes."""
+
+  def __init__(self, height, width, batch, device):
+    who = type(self).__name__
+    self.H, self.W, self.B = int(height), int(width), int(batch)
+    if self.H < 1 or self.W < 1 or self.B < 1:
+      raise ValueError("%s: size %r x %r, batch %r" % (who, height, width, batch))
+    self.device = gpu_device(who, device)
+
+  def _zeros(self, shape, dtype):
+    t = torch.zeros(shape, dtype=dtype, device=self.device)
+    self._buffers_on = t.device                              # with the index that `device` may lack
+    return t
+
+  def _check_map(self, who, name, t, channels=1):
+    check_f32(who, name, t, ((4,), "[B,%s,H,W]" % ("1" if channels == 1 else "C")))
+    check_shape(who, name, t, (self.B, channels, self.H, self.W), self._buffers_on)
+
+  def _fractions(self, counts):
+    """Synchronises.  numpy fp64: int32 counts of pixels as shares of an image."""
+    return counts.cpu().numpy().astype("float64") / float(self.H * self.W)
+
+
 class RowCursor(object):
   """The device-side state of a collector of `capacity` rows: the cursor its kernel appends at and a counter of the rows that did
   not fit (as_cursor_advance_enqueue keeps both), allocated once.  A subclass adds its row buffers, add() and its accessor."""
@@ -26,11 +81,8 @@ class RowCursor(object):
     self.capacity = int(capacity)
     if self.capacity < 1:
       raise ValueError("%s: capacity %r must be at least 1" % (who, capacity))
-    dev = torch.device(device)
-    if dev.type != "cuda":
-      raise RuntimeError("adaptive_stereo: %s lives on the GPU (got %s); there is no CPU path" % (who, dev))
-    self.device = dev
-    self._state = torch.zeros(2, dtype=torch.int32, device=dev)          # cursor, dropped
+    self.device = gpu_device(who, device)
+    self._state = torch.zeros(2, dtype=torch.int32, device=self.device)  # cursor, dropped
     self._cursor, self._dropped = self._state[0:1], self._state[1:2]
 
   def rows_in_use(self):

@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from . import _native as nat
-from .collect import check_f32
+from .collect import check_f32, gpu_device
 
 KINDS = ("pmax", "entropy", "mass", "fcs")
 MAX_BINS = 1024
@@ -99,10 +99,7 @@ class SparsificationCollector(object):
     self.scale = bin_scale(self.bins, self.lo, self.hi)
     if not (np.isfinite(self.scale) and self.scale > 0):
       raise ValueError("SparsificationCollector: bins / (hi - lo) = %r is not a positive fp32 number" % (self.scale,))
-    dev = torch.device(device)
-    if dev.type != "cuda":
-      raise RuntimeError("adaptive_stereo: SparsificationCollector lives on the GPU (got %s); there is no CPU path" % dev)
-    self.device = dev
+    self.device = dev = gpu_device("SparsificationCollector", device)
     K = self.bins
     self._ints = torch.zeros(2 * K + 1, dtype=torch.int64, device=dev)        # count [K] | bad [K] | skipped
     self._err = torch.zeros(K, dtype=torch.float64, device=dev)

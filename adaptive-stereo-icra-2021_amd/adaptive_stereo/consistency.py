@@ -25,7 +25,7 @@ import torch
 from . import _native as nat
 from . import hip_ops
 from .capture import copy_unless_same, refuse_nested, warm_up_and_capture
-from .collect import check_f32
+from .collect import MapOperator, check_f32, check_u8
 
 CODE_NAMES = ("consistent", "occluded", "mismatch", "out_of_view", "bad_input")
 
@@ -89,34 +89,22 @@ def predict_disparity_leftright(feature_net, stereo_net, left, right, output_cos
   return outputs_lr
 
 
-class LeftRightConsistency(object):
+class LeftRightConsistency(MapOperator):
   """The check and the fill for maps [batch,1,height,width].  All output buffers are allocated once; every call overwrites them,
   enqueues only and is graph-capturable.  tol = max(tol_abs, tol_rel * d) in disparity units."""
 
   def __init__(self, height, width, batch=1, tol_abs=1.0, tol_rel=0.0, device="cuda"):
-    self.H, self.W, self.B = int(height), int(width), int(batch)
-    if self.H < 1 or self.W < 1 or self.B < 1:
-      raise ValueError("LeftRightConsistency: size %r x %r, batch %r" % (height, width, batch))
+    super().__init__(height, width, batch, device)
     self.tol_abs, self.tol_rel = float(tol_abs), float(tol_rel)
     if not (np.isfinite(self.tol_abs) and np.isfinite(self.tol_rel) and self.tol_abs >= 0 and self.tol_rel >= 0):
       raise ValueError("LeftRightConsistency: tol_abs %r and tol_rel %r must be finite and not negative" % (tol_abs, tol_rel))
-    dev = torch.device(device)
-    if dev.type != "cuda":
-      raise RuntimeError("adaptive_stereo: LeftRightConsistency lives on the GPU (got %s); there is no CPU path" % dev)
-    self.device = dev
     shape = (2, self.B, 1, self.H, self.W)                 # left view, right view
-    self._code = torch.zeros(shape, dtype=torch.uint8, device=dev)
-    self._valid = torch.zeros(shape, dtype=torch.float32, device=dev)
-    self._diff = torch.zeros(shape, dtype=torch.float32, device=dev)
-    self._counts = torch.zeros(self.B, 2, len(CODE_NAMES), dtype=torch.int32, device=dev)
-    self._filled = torch.zeros(shape[1:], dtype=torch.float32, device=dev)
+    self._code = self._zeros(shape, torch.uint8)
+    self._valid = self._zeros(shape, torch.float32)
+    self._diff = self._zeros(shape, torch.float32)
+    self._counts = self._zeros((self.B, 2, len(CODE_NAMES)), torch.int32)
+    self._filled = self._zeros(shape[1:], torch.float32)
     self._result = LRCheck(self._code[0], self._code[1], self._valid[0], self._valid[1], self._diff[0], self._diff[1], self._counts)
-
-  def _check_map(self, who, name, t):
-    check_f32(who, name, t, ((4,), "[B,1,H,W]"))
-    if tuple(t.shape) != (self.B, 1, self.H, self.W) or t.device != self._code.device:
-      raise RuntimeError("%s: %s must be %s on %s (got %s on %s)" % (who, name, (self.B, 1, self.H, self.W), self._code.device,
-                                                                     tuple(t.shape), t.device))
 
   def check(self, disp_l, disp_r, mirrored=False):
     """LRCheck of views into this object's buffers: code_l, code_r (uint8: 0 consistent, 1 occluded, 2 mismatch, 3 out of view,
@@ -137,11 +125,7 @@ class LeftRightConsistency(object):
     background), the only one where one side has none, 0.0 in a row without any.  out: this object's buffer when None."""
     who = "LeftRightConsistency.fill"
     self._check_map(who, "disp", disp)
-    if not isinstance(code, torch.Tensor) or code.dtype != torch.uint8 or not code.is_contiguous() or \
-       tuple(code.shape) != tuple(disp.shape) or code.device != disp.device:
-      raise RuntimeError("%s: code must be a contiguous uint8 %s tensor on %s (got %s, %s, %s)"
-                         % (who, tuple(disp.shape), disp.device, tuple(getattr(code, "shape", ())), getattr(code, "dtype", None),
-                            getattr(code, "device", None)))
+    check_u8(who, "code", code, disp.shape, disp.device)
     if out is None:
       out = self._filled
     else:
@@ -154,7 +138,7 @@ class LeftRightConsistency(object):
 
   def fractions(self):
     """Synchronises.  numpy fp64 [B,2,5]: the share of each code per image and view in the last check()."""
-    return self._counts.cpu().numpy().astype(np.float64) / float(self.H * self.W)
+    return self._fractions(self._counts)
 
 
 class BothViewInference(object):

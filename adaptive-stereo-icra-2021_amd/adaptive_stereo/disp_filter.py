@@ -19,28 +19,25 @@ include/adaptive_stereo_hip.h.  There is no CPU path.
 """
 import collections
 
-import numpy as np
 import torch
 
 from . import _native as nat
 from . import consistency
-from .collect import check_f32
+from .collect import MapOperator, check_u8, int_in
 
 CODE_NAMES = consistency.CODE_NAMES + ("discontinuity", "speckle")
 
 DispFilter = collections.namedtuple("DispFilter", "code valid jump label size counts")
 
 
-class DisparityFilter(object):
+class DisparityFilter(MapOperator):
   """The edge check and the speckle pass for maps [batch,1,height,width].  All output buffers are allocated once; every call
   overwrites them, enqueues only and is graph-capturable.  An edge is |d - neighbour| > max(tol_abs, tol_rel * d) against a usable
   4-neighbour; a speckle is a 4-connected component of at most max_size pixels, neighbours being joined when they differ by at
   most max_diff (+inf: every usable pair)."""
 
   def __init__(self, height, width, batch=1, tol_abs=1.0, tol_rel=0.0, max_diff=1.0, max_size=200, device="cuda"):
-    self.H, self.W, self.B = int(height), int(width), int(batch)
-    if self.H < 1 or self.W < 1 or self.B < 1:
-      raise ValueError("DisparityFilter: size %r x %r, batch %r" % (height, width, batch))
+    super().__init__(height, width, batch, device)
     if self.H * self.W > 2 ** 31 - 1 or self.B > 65535:
       raise ValueError("DisparityFilter: %d x %d pixels (at most 2^31 - 1) in a batch of %d (at most 65535)" % (self.H, self.W, self.B))
     self.tol_abs, self.tol_rel, self.max_diff = float(tol_abs), float(tol_rel), float(max_diff)
@@ -48,33 +45,21 @@ class DisparityFilter(object):
       raise ValueError("DisparityFilter: tol_abs %r and tol_rel %r must be numbers and not negative" % (tol_abs, tol_rel))
     if not self.max_diff >= 0:
       raise ValueError("DisparityFilter: max_diff %r must be a number and not negative" % (max_diff,))
-    self.max_size = int(max_size)
-    if self.max_size != max_size or not 0 <= self.max_size <= 2 ** 31 - 1:
-      raise ValueError("DisparityFilter: max_size %r must be an integer in 0 .. 2^31 - 1" % (max_size,))
-    dev = torch.device(device)
-    if dev.type != "cuda":
-      raise RuntimeError("adaptive_stereo: DisparityFilter lives on the GPU (got %s); there is no CPU path" % dev)
-    self.device = dev
+    self.max_size = int_in("DisparityFilter", "max_size", max_size, 0, 2 ** 31 - 1)
     shape = (self.B, 1, self.H, self.W)
-    u8 = lambda: torch.zeros(shape, dtype=torch.uint8, device=dev)
-    f32 = lambda: torch.zeros(shape, dtype=torch.float32, device=dev)
-    i32 = lambda: torch.zeros(shape, dtype=torch.int32, device=dev)
-    counts = lambda: torch.zeros(self.B, len(CODE_NAMES), dtype=torch.int32, device=dev)
+    u8 = lambda: self._zeros(shape, torch.uint8)
+    f32 = lambda: self._zeros(shape, torch.float32)
+    i32 = lambda: self._zeros(shape, torch.int32)
+    counts = lambda: self._zeros((self.B, len(CODE_NAMES)), torch.int32)
     self._edges = DispFilter(u8(), f32(), f32(), None, None, counts())            # the speckle pass reads the edge pass's code
     self._speckles = DispFilter(u8(), f32(), None, i32(), i32(), counts())
     self._both = self._speckles._replace(jump=self._edges.jump)
     self._last = None
 
   def _check_maps(self, who, disp, code_in):
-    check_f32(who, "disp", disp, ((4,), "[B,1,H,W]"))
-    shape, dev = (self.B, 1, self.H, self.W), self._edges.code.device
-    if tuple(disp.shape) != shape or disp.device != dev:
-      raise RuntimeError("%s: disp must be %s on %s (got %s on %s)" % (who, shape, dev, tuple(disp.shape), disp.device))
-    if code_in is not None and (not isinstance(code_in, torch.Tensor) or code_in.dtype != torch.uint8 or not code_in.is_contiguous()
-                                or tuple(code_in.shape) != shape or code_in.device != dev):
-      raise RuntimeError("%s: code_in must be a contiguous uint8 %s tensor on %s (got %s, %s, %s)"
-                         % (who, shape, dev, tuple(getattr(code_in, "shape", ())), getattr(code_in, "dtype", None),
-                            getattr(code_in, "device", None)))
+    self._check_map(who, "disp", disp)
+    if code_in is not None:
+      check_u8(who, "code_in", code_in, disp.shape, disp.device)
 
   def edges(self, disp, code_in=None):
     """DispFilter of views into this object's buffers: code (uint8: code_in where non-zero, 4 bad input, 5 discontinuity, else
@@ -113,7 +98,7 @@ class DisparityFilter(object):
     """Synchronises.  numpy fp64 [B,7]: the share of each code per image in the last call."""
     if self._last is None:
       raise RuntimeError("DisparityFilter.fractions: nothing has been filtered yet")
-    return self._last.counts.cpu().numpy().astype(np.float64) / float(self.H * self.W)
+    return self._fractions(self._last.counts)
 
 
 class FilteredBothViewInference(consistency.BothViewInference):

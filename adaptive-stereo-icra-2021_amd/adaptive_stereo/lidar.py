@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import _native as nat
+from .collect import gpu_device
 
 _NUMERIC = frozenset("0123456789.e+- ")
 
@@ -107,9 +108,7 @@ class LidarGroundTruth(object):
     self.B, self.max_points = int(batch), int(max_points)
     if self.B < 1 or self.max_points < 1:
       raise ValueError("LidarGroundTruth: batch %d and max_points %d must be positive" % (self.B, self.max_points))
-    dev = torch.device(device)
-    if dev.type != "cuda":
-      raise RuntimeError("adaptive_stereo: LidarGroundTruth lives on the GPU (got %s); there is no CPU path" % dev)
+    dev = gpu_device("LidarGroundTruth", device)
     lib = nat.load()
     B, H, W = self.B, self.H, self.W
     ws = lib.as_lidar_resolve_workspace(B, H, W)

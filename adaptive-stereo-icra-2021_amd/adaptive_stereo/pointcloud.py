@@ -23,6 +23,7 @@ import ctypes
 import torch
 
 from . import _native as nat
+from .collect import gpu_device
 
 
 class StereoCamera(object):
@@ -112,10 +113,7 @@ class DepthProjector(object):
     self.voxel_size = float(voxel_size)
     self.camera = camera
     self._cam = camera.native(self.s, max_depth, depth_scale, depth_trunc)
-    dev = torch.device(device)
-    if dev.type != "cuda":
-      raise RuntimeError("adaptive_stereo: DepthProjector lives on the GPU (got %s); there is no CPU path" % dev)
-    self.device = dev
+    self.device = dev = gpu_device("DepthProjector", device)
     B, h, w = self.B, self.h, self.w
     self._depth = torch.empty(B, 1, h, w, dtype=torch.float32, device=dev)
     self._xyz = torch.empty(B, 3, h, w, dtype=torch.float32, device=dev)

@@ -27,7 +27,7 @@ import torch
 from . import _native as nat
 from . import lidar
 from .capture import refuse_nested, warm_up_and_capture
-from .collect import check_f32
+from .collect import check_f32, check_shape, check_u8, gpu_device
 from .pointcloud import StereoCamera
 
 
@@ -244,10 +244,7 @@ class Rectifier(object):
     self.B, self.C, self.fill = int(batch), int(channels), float(fill)
     if self.B < 1 or 2 * self.B > 65535 or self.C not in (1, 3):
       raise ValueError("Rectifier: batch %r (1 .. 32767), channels %r (1 or 3)" % (batch, channels))
-    dev = torch.device(device)
-    if dev.type != "cuda":
-      raise RuntimeError("adaptive_stereo: Rectifier lives on the GPU (got %s); there is no CPU path" % dev)
-    self.device = dev
+    self.device = dev = gpu_device("Rectifier", device)
     self.camera = stereo_camera(view_l, view_r, (i0, j0, H, W))
     self._cams = (view_l.native(), view_r.native())
     self._out = torch.zeros(2, self.B, 3, H, W, dtype=torch.float32, device=dev)
@@ -275,9 +272,7 @@ class Rectifier(object):
     if not isinstance(t, torch.Tensor) or not t.is_cuda:
       raise RuntimeError("adaptive_stereo: tensors must live on the GPU (got %s for %s); there is no CPU path"
                          % (getattr(t, "device", type(t)), name))
-    if t.dtype != torch.uint8 or not t.is_contiguous() or tuple(t.shape) != shape or t.device != self._out.device:
-      raise RuntimeError("Rectifier: %s must be a contiguous uint8 %s tensor on %s (got %s, %s, %s)"
-                         % (name, shape, self._out.device, tuple(t.shape), t.dtype, t.device))
+    check_u8("Rectifier", name, t, shape, self._out.device)
 
   def __call__(self, raw_l, raw_r, out=None):
     """-> (left, right) fp32 [B,3,H,W]: this object's buffers, or `out` = (left, right), e.g. BothViewInference.inputs()."""
@@ -289,8 +284,7 @@ class Rectifier(object):
       left, right = out
       for name, t in (("out[0]", left), ("out[1]", right)):
         check_f32("Rectifier", name, t, ((4,), "[B,3,H,W]"), device=self._out.device)
-        if tuple(t.shape) != (self.B, 3, self.H, self.W):
-          raise RuntimeError("Rectifier: %s must be %s (got %s)" % (name, (self.B, 3, self.H, self.W), tuple(t.shape)))
+        check_shape("Rectifier", name, t, (self.B, 3, self.H, self.W), self._out.device)
     with torch.cuda.device(self.device):
       nat.call("as_rectify_pair", nat.ptr(raw_l), nat.ptr(raw_r), self.B, self.H0, self.W0, self.C, self._cams[0], self._cams[1],
                self.i0, self.j0, self.H, self.W, self.fill, nat.ptr(left), nat.ptr(right), nat.stream())

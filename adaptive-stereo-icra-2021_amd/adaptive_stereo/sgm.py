@@ -19,13 +19,12 @@ are fixed op by op in include/adaptive_stereo_hip.h.  There is no CPU path.
 """
 import collections
 
-import numpy as np
 import torch
 
 from . import _native as nat
 from . import disp_filter
 from .capture import copy_unless_same, refuse_nested, warm_up_and_capture
-from .collect import check_f32
+from .collect import MapOperator, check_f32, int_in
 from .consistency import LeftRightConsistency
 
 CODE_NAMES = disp_filter.CODE_NAMES + ("not_unique",)
@@ -33,14 +32,7 @@ CODE_NAMES = disp_filter.CODE_NAMES + ("not_unique",)
 SGMResult = collections.namedtuple("SGMResult", "disp_l disp_r code_l code_r counts")
 
 
-def _int_in(who, name, value, lo, hi):
-  v = int(value)
-  if v != value or not lo <= v <= hi:
-    raise ValueError("%s: %s %r must be an integer in %d .. %d" % (who, name, value, lo, hi))
-  return v
-
-
-class SemiGlobalMatcher(object):
+class SemiGlobalMatcher(MapOperator):
   """Census, aggregation and selection for pairs [batch,channels,height,width].  All buffers, the aggregation volume included
   (2 * batch * height * width * maxdisp bytes), are allocated once; every call overwrites them, enqueues only and is
   graph-capturable.  p1, p2: the penalties of a disparity step of one and of more than one along a path; uniqueness: the margin in
@@ -49,42 +41,33 @@ class SemiGlobalMatcher(object):
 
   def __init__(self, height, width, batch=1, maxdisp=192, p1=10, p2=120, paths=8, uniqueness=5, channels=3, device="cuda"):
     who = "SemiGlobalMatcher"
-    self.H, self.W, self.B = int(height), int(width), int(batch)
-    if self.H < 1 or self.W < 1 or self.B < 1:
-      raise ValueError("%s: size %r x %r, batch %r" % (who, height, width, batch))
-    self.D = _int_in(who, "maxdisp", maxdisp, 1, 256)
+    super().__init__(height, width, batch, device)
+    self.D = int_in(who, "maxdisp", maxdisp, 1, 256)
     if self.H * self.W * self.D > 2 ** 31 - 1 or self.B > 65535:
       raise ValueError("%s: %d x %d pixels x %d disparities (at most 2^31 - 1) in a batch of %d (at most 65535)"
                        % (who, self.H, self.W, self.D, self.B))
-    self.p1 = _int_in(who, "p1", p1, 0, 255)
-    self.p2 = _int_in(who, "p2", p2, self.p1, 255)
+    self.p1 = int_in(who, "p1", p1, 0, 255)
+    self.p2 = int_in(who, "p2", p2, self.p1, 255)
     if paths not in (4, 8):
       raise ValueError("%s: paths %r must be 4 or 8" % (who, paths))
     self.paths = int(paths)
-    self.uniqueness = _int_in(who, "uniqueness", uniqueness, 0, 99)
+    self.uniqueness = int_in(who, "uniqueness", uniqueness, 0, 99)
     if channels not in (1, 3):
       raise ValueError("%s: channels %r must be 1 or 3" % (who, channels))
     self.C = int(channels)
-    dev = torch.device(device)
-    if dev.type != "cuda":
-      raise RuntimeError("adaptive_stereo: SemiGlobalMatcher lives on the GPU (got %s); there is no CPU path" % dev)
-    self.device = dev
     shape = (self.B, 1, self.H, self.W)
-    self._census = torch.zeros((2, self.B, self.H, self.W), dtype=torch.int64, device=dev)        # left, right: uint64 words
+    self._census = self._zeros((2, self.B, self.H, self.W), torch.int64)                          # left, right: uint64 words
     nbytes = nat.load().as_sgm_workspace(self.B, self.H, self.W, self.D)
     if nbytes <= 0:
       raise RuntimeError("%s: as_sgm_workspace refused %d x %d x %d x %d" % (who, self.B, self.H, self.W, self.D))
-    self._volume = torch.zeros(nbytes // 2, dtype=torch.int16, device=dev)                        # uint16 [B][H][W][D]
-    f32 = lambda: torch.zeros(shape, dtype=torch.float32, device=dev)
-    u8 = lambda: torch.zeros(shape, dtype=torch.uint8, device=dev)
-    self._result = SGMResult(f32(), f32(), u8(), u8(), torch.zeros(self.B, 2, len(CODE_NAMES), dtype=torch.int32, device=dev))
+    self._volume = self._zeros(nbytes // 2, torch.int16)                                          # uint16 [B][H][W][D]
+    f32 = lambda: self._zeros(shape, torch.float32)
+    u8 = lambda: self._zeros(shape, torch.uint8)
+    self._result = SGMResult(f32(), f32(), u8(), u8(), self._zeros((self.B, 2, len(CODE_NAMES)), torch.int32))
     self._ran = False
 
   def _check_image(self, who, name, img):
-    check_f32(who, name, img, ((4,), "[B,C,H,W]"))
-    shape = (self.B, self.C, self.H, self.W)
-    if tuple(img.shape) != shape or img.device != self._volume.device:
-      raise RuntimeError("%s: %s must be %s on %s (got %s on %s)" % (who, name, shape, self._volume.device, tuple(img.shape), img.device))
+    self._check_map(who, name, img, self.C)
 
   def _census_into(self, img, out):
     with torch.cuda.device(self.device):
@@ -124,7 +107,7 @@ class SemiGlobalMatcher(object):
     """Synchronises.  numpy fp64 [B,2,8]: the share of each code per image and view in the last call."""
     if not self._ran:
       raise RuntimeError("SemiGlobalMatcher.fractions: nothing has been matched yet")
-    return self._result.counts.cpu().numpy().astype(np.float64) / float(self.H * self.W)
+    return self._fractions(self._result.counts)
 
 
 class ProxyLabeler(object):

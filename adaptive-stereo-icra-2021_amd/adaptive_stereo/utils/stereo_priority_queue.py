@@ -18,6 +18,7 @@ duplicates among its members only, so an index may be offered again once it has 
 import torch
 
 from .. import _native as nat
+from ..collect import gpu_device
 
 
 class StereoPriorityQueue(object):
@@ -76,9 +77,7 @@ class DevicePriorityQueue(object):
   def __init__(self, max_size, min_heap=True, device="cuda"):
     if max_size < 1:
       raise ValueError("DevicePriorityQueue: max_size must be at least 1")
-    dev = torch.device(device)
-    if dev.type != "cuda":
-      raise RuntimeError("adaptive_stereo: DevicePriorityQueue lives on the GPU (got %s); there is no CPU path" % dev)
+    dev = gpu_device("DevicePriorityQueue", device)
     self.max_size = int(max_size)
     self.min_heap = bool(min_heap)
     self.multiplier = 1 if min_heap else -1

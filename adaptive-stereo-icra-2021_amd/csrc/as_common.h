@@ -113,7 +113,7 @@ static inline int as_launch_lds(const void* fn, AsPerDevice& once, int attr_byte
 
 static inline int as_div_up(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
-// Byte ranges of an entry point's arguments (disp_filter.hip, sgm.hip); a NULL pointer overlaps nothing.
+// Byte ranges of an entry point's arguments; a NULL pointer overlaps nothing.
 struct AsRange {
   const void* p;
   int64_t bytes;
@@ -141,6 +141,15 @@ __device__ inline double wave_sum_d(double v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+__device__ __forceinline__ int wave_sum_i(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// The quiet NaN every contract names for "no value here" (include/adaptive_stereo_hip.h).
+#define AS_QNAN_BITS 0x7FC00000
+__device__ inline float as_qnan() { return __int_as_float(AS_QNAN_BITS); }
 
 // ---- shared by the three fp64 BatchNorm merges (bn_act.hip's finalize, bn_merge.h, trunk.hip) ---------------------------
 // The pivot of the one-pass merge is the mean of the first partial with a count above 0: an empty partial 0 (mean 0) as the

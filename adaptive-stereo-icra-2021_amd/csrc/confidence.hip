@@ -61,7 +61,7 @@ __global__ __launch_bounds__(256) void disp_confidence_kernel(const float* __res
   float c = 1.f - Hn / logf((float)D);
   c = fminf(fmaxf(c, 0.f), 1.f);
   if (D == 1) { p = 1.f; ms = 1.f; c = 1.f; }
-  if (bad) p = ms = c = __int_as_float(0x7FC00000);
+  if (bad) p = ms = c = as_qnan();
 
   const long at = (long)b * HW + pix;
   if (pmax) pmax[at] = p;

@@ -53,7 +53,7 @@ __global__ __launch_bounds__(CVP_THREADS) void cv_probe_kernel(const float* __re
   const long row = (long)(cursor ? *cursor : 0) + b;
   if (row < 0 || row >= capacity) return;                  // (uniform) the row has no place: the cursor launch counts it
   const float* vol = logits + (long)b * D * HW;
-  const float nan = __int_as_float(0x7FC00000);
+  const float nan = as_qnan();
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 
   unsigned long long best_hi = 0, best_lo = 0;              // 0: no pixel yet (every real key is above 2^54)

@@ -9,9 +9,8 @@
 // DF_GROUPS / B, B).  A wave is 64 consecutive pixels of one row.
 //
 //   disp_edge_kernel      a pixel's own disparity and its four neighbours' (the neighbouring lanes' and rows' loads, out of the
-//                         cache); max |d - d_q| over the usable neighbours against max(tol_abs, tol_rel * d).  The seven counts as
-//                         lr_check_kernel keeps them: per lane, summed over the wave, LDS integers, one global integer atomic per
-//                         code and workgroup onto counts the entry point has zeroed with a small launch (as_zero_i32_enqueue).
+//                         cache); max |d - d_q| over the usable neighbours against max(tol_abs, tol_rel * d).  The seven counts
+//                         go the way of code_maps.h (as_counts_*).
 //
 // The speckle filter is connected-component labelling by union-find over the pixel index, label[] being the parent links and
 // size[] the root counters (no further workspace).  A parent is never larger than its pixel, a union links the larger root under
@@ -35,7 +34,7 @@
 //                         the whole image is then one add per workgroup; added per wave and row, its 7500 adds an image on one
 //                         address, which the memory serves one after the other, were most of the pass (measured).
 //   speckle_apply_kernel  size = the root's counter (roots keep theirs and are not stored again), the code, valid and counts.
-#include "as_common.h"
+#include "code_maps.h"
 
 #pragma clang fp contract(off)
 
@@ -44,7 +43,6 @@
 #define DF_WAVE 64
 #define DF_CODES 7                  // 0 keep, 1-3 as as_lr_check, 4 bad input, 5 discontinuity, 6 speckle
 #define DF_GROUPS 2048              // workgroups over all images (8 a CU: every one resident at once)
-#define DF_QNAN 0x7FC00000
 
 // (y, x) of every pixel slot of the workgroup's tiles, all 256 lanes of every row together (x may lie beyond W - 1)
 template <typename F>
@@ -58,35 +56,20 @@ static __device__ inline void df_rows(int H, int xblocks, F f) {
   }
 }
 
-// as_lr_check's step 1 on top of an incoming code: -0.0 is usable
+// usable on top of an incoming code
 static __device__ inline bool df_usable(const uint8_t* __restrict__ cin, long at, float d) {
-  return (cin == nullptr || cin[at] == 0) && d >= 0.f && d != INFINITY;
+  return (cin == nullptr || cin[at] == 0) && as_disp_usable(d);
 }
 
 static inline dim3 df_grid(int B, int H, int W) {
-  const int64_t tiles = (int64_t)as_div_up(H, DF_ROWS) * as_div_up(W, DF_SPAN);
-  const int64_t per_image = as_div_up(DF_GROUPS, B);
-  return dim3((unsigned)(tiles < per_image ? tiles : per_image), B);
+  return as_strided_grid((int64_t)as_div_up(H, DF_ROWS) * as_div_up(W, DF_SPAN), DF_GROUPS, B);
 }
 
-// the seven per-lane counts of a workgroup onto counts[b][7]: wave sums, LDS integers, one global atomic per code
+// the seven per-lane counts of a workgroup onto counts[b][7]
 static __device__ inline void df_add_counts(const int (&mine)[DF_CODES], int* s_count, int32_t* counts) {
 #pragma unroll
-  for (int c = 0; c < DF_CODES; ++c) {
-    int v = mine[c];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    if ((threadIdx.x & 63) == 0 && v) atomicAdd(&s_count[c], v);
-  }
-  __syncthreads();
-  if (threadIdx.x < DF_CODES && s_count[threadIdx.x]) atomicAdd(counts + blockIdx.y * DF_CODES + threadIdx.x, s_count[threadIdx.x]);
-}
-
-static int df_clear_counts(const char* who, int32_t* counts, int B, hipStream_t st) {
-  if (counts == nullptr) return AS_OK;
-  as_zero_i32_enqueue(st, counts, B * DF_CODES);
-  AS_CHECK_LAUNCH(who);
-  return AS_OK;
+  for (int c = 0; c < DF_CODES; ++c) as_counts_add(&s_count[c], mine[c]);
+  as_counts_flush(s_count, DF_CODES, counts + blockIdx.y * DF_CODES);
 }
 
 // ------------------------------------------------------------------------------------------------ the discontinuity check
@@ -103,8 +86,7 @@ struct DfEdgeArgs {
 
 __global__ __launch_bounds__(DF_SPAN) void disp_edge_kernel(DfEdgeArgs a) {
   __shared__ int s_count[DF_CODES];
-  if (threadIdx.x < DF_CODES) s_count[threadIdx.x] = 0;
-  __syncthreads();
+  as_counts_begin(s_count, DF_CODES);
   const int H = a.H, W = a.W;
   const long image = (long)blockIdx.y * H * W;
   const float* D = a.disp + image;
@@ -115,11 +97,11 @@ __global__ __launch_bounds__(DF_SPAN) void disp_edge_kernel(DfEdgeArgs a) {
     const long at = (long)y * W + x;
     const float d = D[at];
     const int cin = K ? K[at] : 0;
-    float e = __int_as_float(DF_QNAN);
+    float e = as_qnan();
     int code = cin;
     if (cin == 0) {
       code = 4;
-      if (d >= 0.f && d != INFINITY) {
+      if (as_disp_usable(d)) {
         const float rel = a.tol_rel * d;
         const float tol = fmaxf(a.tol_abs, rel);
         bool over = false;
@@ -148,17 +130,10 @@ __global__ __launch_bounds__(DF_SPAN) void disp_edge_kernel(DfEdgeArgs a) {
   df_add_counts(mine, s_count, a.counts);
 }
 
-static int df_check_shape(const char* who, int B, int H, int W) {
-  AS_CHECK_ARG(B > 0 && H > 0 && W > 0, "%s: bad shape (B %d, H %d, W %d)", who, B, H, W);
-  AS_CHECK_ARG((int64_t)H * W <= 0x7FFFFFFF, "%s: H * W = %lld overflows an int32 pixel index", who, (long long)H * W);
-  AS_CHECK_ARG(B <= 65535, "%s: B %d above 65535, the grid's second extent", who, B);
-  return AS_OK;
-}
-
 extern "C" int as_disp_edge_check(const float* disp, const uint8_t* code_in, int B, int H, int W, float tol_abs, float tol_rel,
                                   uint8_t* code, float* valid, float* jump, int32_t* counts, void* stream) {
   AS_CHECK_ARG(disp, "as_disp_edge_check: null pointer");
-  if (int rc = df_check_shape("as_disp_edge_check", B, H, W)) return rc;
+  if (int rc = as_check_images("as_disp_edge_check", B, H, W, true)) return rc;
   AS_CHECK_ARG(tol_abs >= 0.f && tol_rel >= 0.f, "as_disp_edge_check: tol_abs %g and tol_rel %g must be numbers and not negative",
                tol_abs, tol_rel);
   AS_CHECK_ARG(code || valid || jump || counts, "as_disp_edge_check: no output requested");
@@ -167,7 +142,7 @@ extern "C" int as_disp_edge_check(const float* disp, const uint8_t* code_in, int
   const AsRange r[] = {{disp, n * 4}, {code_in, n}, {code, n}, {valid, n * 4}, {jump, n * 4}, {counts, (int64_t)B * DF_CODES * 4}};
   AS_CHECK_ARG(as_disjoint(r, 2, 6), "as_disp_edge_check: an output may alias neither an input nor another output (overlapping ranges)");
   hipStream_t st = (hipStream_t)stream;
-  if (int rc = df_clear_counts("as_disp_edge_check", counts, B, st)) return rc;
+  if (int rc = as_clear_counts("as_disp_edge_check", counts, B * DF_CODES, st)) return rc;
   DfEdgeArgs a;
   a.disp = disp; a.code_in = code_in; a.code = code; a.valid = valid; a.jump = jump; a.counts = counts;
   a.H = H; a.W = W; a.xblocks = as_div_up(W, DF_SPAN);
@@ -327,8 +302,7 @@ __global__ __launch_bounds__(DF_SPAN) void speckle_count_kernel(DfSpeckleArgs a)
 
 __global__ __launch_bounds__(DF_SPAN) void speckle_apply_kernel(DfSpeckleArgs a) {
   __shared__ int s_count[DF_CODES];
-  if (threadIdx.x < DF_CODES) s_count[threadIdx.x] = 0;
-  __syncthreads();
+  as_counts_begin(s_count, DF_CODES);
   const int W = a.W;
   const long image = (long)blockIdx.y * a.H * W;
   const uint8_t* K = a.code_in ? a.code_in + image : nullptr;
@@ -358,7 +332,7 @@ __global__ __launch_bounds__(DF_SPAN) void speckle_apply_kernel(DfSpeckleArgs a)
 extern "C" int as_disp_speckle(const float* disp, const uint8_t* code_in, int B, int H, int W, float max_diff, int max_size,
                                int32_t* label, int32_t* size, uint8_t* code, float* valid, int32_t* counts, void* stream) {
   AS_CHECK_ARG(disp && label && size, "as_disp_speckle: null pointer");
-  if (int rc = df_check_shape("as_disp_speckle", B, H, W)) return rc;
+  if (int rc = as_check_images("as_disp_speckle", B, H, W, true)) return rc;
   AS_CHECK_ARG(max_diff >= 0.f, "as_disp_speckle: max_diff %g must be a number and not negative", max_diff);
   AS_CHECK_ARG(max_size >= 0, "as_disp_speckle: max_size %d must not be negative", max_size);
   AS_CHECK_ARG((((uintptr_t)label | (uintptr_t)size | (uintptr_t)counts) & 3) == 0,
@@ -368,7 +342,7 @@ extern "C" int as_disp_speckle(const float* disp, const uint8_t* code_in, int B,
                        {counts, (int64_t)B * DF_CODES * 4}};
   AS_CHECK_ARG(as_disjoint(r, 2, 7), "as_disp_speckle: an output may alias neither an input nor another output (overlapping ranges)");
   hipStream_t st = (hipStream_t)stream;
-  if (int rc = df_clear_counts("as_disp_speckle", counts, B, st)) return rc;
+  if (int rc = as_clear_counts("as_disp_speckle", counts, B * DF_CODES, st)) return rc;
   DfSpeckleArgs a;
   a.disp = disp; a.code_in = code_in; a.label = label; a.size = size; a.code = code; a.valid = valid; a.counts = counts;
   a.H = H; a.W = W; a.xblocks = as_div_up(W, DF_SPAN); a.max_size = max_size;

@@ -34,7 +34,7 @@
 // The four elements of vector k of the row's 16-byte grid; elements outside [0, W) come back as NaN (invalid by the contract's
 // own rule, so they enter no bin and no difference).  `mis` = how many floats the row start lies past a 16-byte boundary.
 __device__ inline f32x4 ent_load(const float* __restrict__ row, int W, int mis, int k, bool active) {
-  const float nan = __int_as_float(0x7FC00000);
+  const float nan = as_qnan();
   f32x4 r = {nan, nan, nan, nan};
   if (!active) return r;
   const int x0 = 4 * k - mis;
@@ -218,7 +218,7 @@ __global__ __launch_bounds__(ENT_THREADS) void image_entropy_kernel(const float*
       for (int i = 0; i < 32; ++i) s += t[i];
     }
     float out = (float)(-s);
-    if (col == 1 && W == 1) out = __int_as_float(0x7FC00000);  // 0 / 0 in the reference's probabilities
+    if (col == 1 && W == 1) out = as_qnan();  // 0 / 0 in the reference's probabilities
     const long r = (long)(cursor ? *cursor : 0) + b;
     if (r >= 0 && r < capacity) scores[2 * r + col] = out;
   }

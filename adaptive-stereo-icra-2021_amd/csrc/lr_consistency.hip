@@ -14,10 +14,9 @@
 //   lr_check_kernel          one lane per pixel and view, lanes along x; a workgroup strides over the (row, 256 columns) tiles of
 //                            one image and view, grid (about 2048 / 2B, B, 2): a coalesced load of the pixel's own disparity and
 //                            a gather of two neighbours out of the other view's row, which the neighbouring workgroups stream
-//                            through the cache.  The five counts are kept per lane, summed over the wave, added to LDS integers
-//                            and end as one global integer atomic per code and workgroup onto counts the entry point has zeroed
-//                            with a small launch (as_zero_i32_enqueue): exact in any order.  The counters of a batch share one or two cache lines,
-//                            where atomics serialise, so the workgroups are kept to about 2048 instead of one per tile.
+//                            through the cache.  The five counts go the way of code_maps.h (as_counts_*).  The counters of a batch
+//                            share one or two cache lines, where atomics serialise, so the workgroups are kept to about 2048
+//                            instead of one per tile.
 //   lr_fill_kernel           one workgroup of 256 lanes per row, FILL_ITEMS pixels per lane, so a pass covers FILL_SPAN = 1024
 //                            pixels.  "The last code-0 value so far" is an associative operator (the right operand wins when it
 //                            holds a value): FILL_ITEMS serial steps in registers, an inclusive scan over the wave with
@@ -25,7 +24,7 @@
 //                            forward scan leaves every pixel's left neighbour in `out`; the backward scan is the same code over
 //                            the mirrored index and picks the smaller of the two.  Whether a pixel has a left neighbour at all
 //                            is "it lies right of the row's first code-0 pixel", which the forward scan reduces on the way.
-#include "as_common.h"
+#include "code_maps.h"
 
 #pragma clang fp contract(off)
 
@@ -36,7 +35,6 @@
 #define FILL_ITEMS 4                // tests/lr_consistency_ref.py places its boundary cases by FILL_SPAN (1024) and FILL_WAVE (256 =
                                     // 64 * FILL_ITEMS): change them there, and the 1024 in the header, together with this
 #define FILL_SPAN (LR_THREADS * FILL_ITEMS)
-#define LR_QNAN 0x7FC00000
 
 // ------------------------------------------------------------------------------------------------ mirror, flip
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -82,12 +80,6 @@ static inline int lr_vector_width(int W, const void* a, const void* b, const voi
 
 // `rows` rows of W floats as these kernels cover them: ceil(W / 256) workgroups a row at one float a lane (the most), all in a 1-D
 // grid.  The product is taken in double, where int32 factors cannot overflow; what passes is exact in int64.
-// two byte ranges share at least one byte
-static inline bool lr_overlap(const void* a, int64_t a_bytes, const void* b, int64_t b_bytes) {
-  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-  return pa < pb + (uintptr_t)b_bytes && pb < pa + (uintptr_t)a_bytes;
-}
-
 static inline bool lr_rows_ok(double rows, int W) { return rows * as_div_up(W, LR_THREADS) <= 2147483647.0; }
 
 template <int V>
@@ -105,10 +97,8 @@ extern "C" int as_mirror_pair(const float* left, const float* right, int B, int 
   AS_CHECK_ARG(lr_rows_ok((double)B * C * H, W), "as_mirror_pair: %.0f rows of %d elements exceed the grid", (double)B * C * H, W);
   const int64_t rows = (int64_t)B * C * H;
   const int64_t in_bytes = rows * W * 4, out_bytes = 2 * in_bytes;
-  AS_CHECK_ARG(!lr_overlap(left_batch, out_bytes, right_batch, out_bytes) && !lr_overlap(left_batch, out_bytes, left, in_bytes) &&
-               !lr_overlap(left_batch, out_bytes, right, in_bytes) && !lr_overlap(right_batch, out_bytes, left, in_bytes) &&
-               !lr_overlap(right_batch, out_bytes, right, in_bytes),
-               "as_mirror_pair: the outputs may alias neither each other nor an input (overlapping ranges)");
+  const AsRange r[] = {{left, in_bytes}, {right, in_bytes}, {left_batch, out_bytes}, {right_batch, out_bytes}};
+  AS_CHECK_ARG(as_disjoint(r, 2, 4), "as_mirror_pair: the outputs may alias neither each other nor an input (overlapping ranges)");
   hipStream_t st = (hipStream_t)stream;
   switch (lr_vector_width(W, left, right, left_batch, right_batch)) {
     case 4: mirror_pair_launch<4>(st, left, right, rows, W, left_batch, right_batch); break;
@@ -131,7 +121,8 @@ extern "C" int as_flip_w(const float* src, int64_t planes, int H, int W, float* 
                (long long)planes, H, W);
   AS_CHECK_ARG(lr_rows_ok((double)planes * H, W), "as_flip_w: %.0f rows of %d elements exceed the grid", (double)planes * H, W);
   const int64_t rows = planes * H;
-  AS_CHECK_ARG(!lr_overlap(src, rows * W * 4, dst, rows * W * 4), "as_flip_w: dst may not alias src (overlapping ranges)");
+  const AsRange r[] = {{src, rows * W * 4}, {dst, rows * W * 4}};
+  AS_CHECK_ARG(as_disjoint(r, 1, 2), "as_flip_w: dst may not alias src (overlapping ranges)");
   hipStream_t st = (hipStream_t)stream;
   switch (lr_vector_width(W, src, dst)) {
     case 4: flip_w_launch<4>(st, src, rows, W, dst); break;
@@ -155,8 +146,7 @@ struct LrCheckArgs {
 
 __global__ __launch_bounds__(LR_THREADS) void lr_check_kernel(LrCheckArgs a) {
   __shared__ int s_count[LR_CODES];
-  if (threadIdx.x < LR_CODES) s_count[threadIdx.x] = 0;
-  __syncthreads();
+  as_counts_begin(s_count, LR_CODES);
 
   const int b = blockIdx.y, view = blockIdx.z;                         // view 0: left pixels sampled in the right map, 1: the converse
   const int W = a.W;
@@ -171,9 +161,9 @@ __global__ __launch_bounds__(LR_THREADS) void lr_check_kernel(LrCheckArgs a) {
     const float* L = a.disp[0] + row * W;
     const float* R = a.disp[1] + row * W;
     const float d = view == 0 ? L[x] : R[abs(mir - x)];
-    float e = __int_as_float(LR_QNAN);
+    float e = as_qnan();
     int code = 4;
-    if (d >= 0.f && d != INFINITY) {
+    if (as_disp_usable(d)) {
       const float u = view == 0 ? (float)x - d : (float)x + d;
       code = 3;
       if (view == 0 ? !(u < 0.f) : !(u > (float)(W - 1))) {            // 0 <= u <= W - 1 from here on
@@ -197,11 +187,13 @@ __global__ __launch_bounds__(LR_THREADS) void lr_check_kernel(LrCheckArgs a) {
     const long at = row * W + x;
     if (a.code[view]) a.code[view][at] = (uint8_t)code;
     if (a.valid[view]) a.valid[view][at] = code == 0 ? 1.f : 0.f;
-    if (a.diff[view]) a.diff[view][at] = code >= 3 ? __int_as_float(LR_QNAN) : e;
+    if (a.diff[view]) a.diff[view][at] = code >= 3 ? as_qnan() : e;
 #pragma unroll
     for (int c = 0; c < LR_CODES; ++c) mine[c] += code == c;
   }
   if (a.counts == nullptr) return;                                     // uniform: no lane waits below
+  // as_counts_add, written out: through the helper the compiler hoists the lanes' index arithmetic out of this loop and the tile
+  // loop above comes out two instructions longer
 #pragma unroll
   for (int c = 0; c < LR_CODES; ++c) {
     int v = mine[c];
@@ -209,19 +201,16 @@ __global__ __launch_bounds__(LR_THREADS) void lr_check_kernel(LrCheckArgs a) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     if ((threadIdx.x & 63) == 0 && v) atomicAdd(&s_count[c], v);
   }
-  __syncthreads();
-  if (threadIdx.x < LR_CODES && s_count[threadIdx.x]) atomicAdd(a.counts + (b * 2 + view) * LR_CODES + threadIdx.x, s_count[threadIdx.x]);
+  as_counts_flush(s_count, LR_CODES, a.counts + (b * 2 + view) * LR_CODES);
 }
 
 extern "C" int as_lr_check(const float* disp_l, const float* disp_r, int mirrored, int B, int H, int W, float tol_abs, float tol_rel,
                            uint8_t* code_l, uint8_t* code_r, float* valid_l, float* valid_r, float* diff_l, float* diff_r,
                            int32_t* counts, void* stream) {
   AS_CHECK_ARG(disp_l && disp_r, "as_lr_check: null pointer");
-  AS_CHECK_ARG(B > 0 && H > 0 && W > 0, "as_lr_check: bad shape (B %d, H %d, W %d)", B, H, W);
+  if (int rc = as_check_images("as_lr_check", B, H, W, true)) return rc;
   AS_CHECK_ARG(W <= LR_MAX_W, "as_lr_check: W %d above 2^24, where a column index is no longer an exact fp32 number", W);
-  AS_CHECK_ARG((int64_t)H * W <= 0x7FFFFFFF, "as_lr_check: H * W = %lld overflows an int32 count", (long long)H * W);
   const int xblocks = as_div_up(W, LR_THREADS);
-  AS_CHECK_ARG(B <= 65535, "as_lr_check: B %d above 65535, the grid's second extent", B);
   AS_CHECK_ARG((int64_t)H * xblocks <= 0x7FFFFFFF, "as_lr_check: %lld tiles an image overflow an int32", (long long)H * xblocks);
   AS_CHECK_ARG(mirrored == 0 || mirrored == 1, "as_lr_check: mirrored %d (0 or 1)", mirrored);
   AS_CHECK_ARG(tol_abs >= 0.f && tol_abs - tol_abs == 0.f && tol_rel >= 0.f && tol_rel - tol_rel == 0.f,
@@ -229,10 +218,7 @@ extern "C" int as_lr_check(const float* disp_l, const float* disp_r, int mirrore
   AS_CHECK_ARG(code_l || code_r || valid_l || valid_r || diff_l || diff_r || counts, "as_lr_check: no output requested");
   AS_CHECK_ARG(!counts || ((uintptr_t)counts & 3) == 0, "as_lr_check: counts must be 4-byte aligned");
   hipStream_t st = (hipStream_t)stream;
-  if (counts) {
-    as_zero_i32_enqueue(st, counts, B * 2 * LR_CODES);
-    AS_CHECK_LAUNCH("as_lr_check");
-  }
+  if (int rc = as_clear_counts("as_lr_check", counts, B * 2 * LR_CODES, st)) return rc;
   LrCheckArgs a;
   a.disp[0] = disp_l; a.disp[1] = disp_r;
   a.code[0] = code_l; a.code[1] = code_r;
@@ -243,9 +229,7 @@ extern "C" int as_lr_check(const float* disp_l, const float* disp_r, int mirrore
   a.tol_abs = tol_abs; a.tol_rel = tol_rel;
   // a workgroup strides over its image's tiles: about LR_CHECK_GROUPS of them in all, so that the five integer atomics each ends
   // with stay a few thousand on one cache line instead of one set per tile
-  const int64_t tiles = (int64_t)H * xblocks;
-  const int64_t per_image = as_div_up(LR_CHECK_GROUPS, 2 * (int64_t)B);
-  hipLaunchKernelGGL(lr_check_kernel, dim3((unsigned)(tiles < per_image ? tiles : per_image), B, 2), dim3(LR_THREADS), 0, st, a);
+  hipLaunchKernelGGL(lr_check_kernel, as_strided_grid((int64_t)H * xblocks, LR_CHECK_GROUPS, B, 2), dim3(LR_THREADS), 0, st, a);
   AS_CHECK_LAUNCH("as_lr_check");
   return AS_OK;
 }
@@ -358,8 +342,8 @@ extern "C" int as_lr_fill(const float* disp, const uint8_t* code, int B, int H, 
   AS_CHECK_ARG((int64_t)B * H <= 0x7FFFFFFF, "as_lr_fill: %lld rows exceed the grid", (long long)B * H);
   AS_CHECK_ARG(W <= 0x7FFFFFFF - FILL_SPAN, "as_lr_fill: W %d overflows the padded column index", W);
   const int64_t n = (int64_t)B * H * W;
-  AS_CHECK_ARG(!lr_overlap(out, n * 4, disp, n * 4) && !lr_overlap(out, n * 4, code, n),
-               "as_lr_fill: out may not alias disp or code (overlapping ranges)");
+  const AsRange r[] = {{disp, n * 4}, {code, n}, {out, n * 4}};
+  AS_CHECK_ARG(as_disjoint(r, 2, 3), "as_lr_fill: out may not alias disp or code (overlapping ranges)");
   hipLaunchKernelGGL(lr_fill_kernel, dim3(B * H), dim3(LR_THREADS), 0, (hipStream_t)stream, disp, code, W, out);
   AS_CHECK_LAUNCH("as_lr_fill");
   return AS_OK;

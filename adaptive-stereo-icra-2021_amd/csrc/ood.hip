@@ -32,7 +32,7 @@ __global__ __launch_bounds__(FCS_THREADS) void fcs_scores_kernel(const float* __
   const int b = blockIdx.x;
   const float* vol = logits + (long)b * D * HW;
   const bool want_median = fcs_median || scores;        // (uniform)
-  const float nan = __int_as_float(0x7FC00000);
+  const float nan = as_qnan();
   const int rank = (D - 1) / 2;
   double acc_mean = 0.0, acc_med = 0.0;
 

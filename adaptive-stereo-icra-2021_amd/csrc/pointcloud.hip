@@ -139,7 +139,7 @@ __global__ __launch_bounds__(256) void pointcloud_kernel(const float* __restrict
   if (inside) {
     if (depth_out) depth_out[(long)b * hw + idx] = depth;
     if (xyz_out) {
-      const float nan = __int_as_float(0x7FC00000);
+      const float nan = as_qnan();
       float* q = xyz_out + (long)b * 3 * hw + idx;
       q[0] = valid ? x : nan;
       q[hw] = valid ? y : nan;

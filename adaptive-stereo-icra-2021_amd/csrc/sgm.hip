@@ -24,9 +24,8 @@
 //                        paths, in chunks 5.4 ms (profiles/sgm_timing.txt).
 //   sgm_select_kernel    a group per pixel: the left column S(y,x,.) and the right one S(y,x+d,d), arg-min by a min over
 //                        (value << 9 | d) across the group, the uniqueness test as an OR across it, the two neighbours of the winner
-//                        fetched from the lanes that hold them.  The counts as as_disp_speckle keeps them: per lane, wave sums, LDS
-//                        integers, one global integer atomic per slot and workgroup.
-#include "as_common.h"
+//                        fetched from the lanes that hold them.  The counts go the way of code_maps.h (as_counts_*).
+#include "code_maps.h"
 
 #pragma clang fp contract(off)
 
@@ -99,14 +98,8 @@ __global__ __launch_bounds__(SGM_BLOCK) void sgm_census_kernel(SgmCensusArgs a) 
   }
 }
 
-static int sgm_check_shape(const char* who, int B, int H, int W) {
-  AS_CHECK_ARG(B > 0 && H > 0 && W > 0, "%s: bad shape (B %d, H %d, W %d)", who, B, H, W);
-  AS_CHECK_ARG(B <= 65535, "%s: B %d above 65535, the grid's second extent", who, B);
-  return AS_OK;
-}
-
 static int sgm_check_volume(const char* who, int B, int H, int W, int D) {
-  if (int rc = sgm_check_shape(who, B, H, W)) return rc;
+  if (int rc = as_check_images(who, B, H, W, false)) return rc;              // H * W * D below bounds H * W
   AS_CHECK_ARG(D >= 1 && D <= SGM_MAX_D, "%s: D %d outside 1 .. %d", who, D, SGM_MAX_D);
   AS_CHECK_ARG((int64_t)H * W * D <= 0x7FFFFFFF, "%s: H * W * D = %lld overflows an int32 index into an image's volume", who,
                (long long)H * W * D);
@@ -115,9 +108,8 @@ static int sgm_check_volume(const char* who, int B, int H, int W, int D) {
 
 extern "C" int as_sgm_census(const float* img, int B, int C, int H, int W, uint64_t* census, void* stream) {
   AS_CHECK_ARG(img && census, "as_sgm_census: null pointer");
-  if (int rc = sgm_check_shape("as_sgm_census", B, H, W)) return rc;
+  if (int rc = as_check_images("as_sgm_census", B, H, W, true)) return rc;
   AS_CHECK_ARG(C == 1 || C == 3, "as_sgm_census: C %d outside {1, 3}", C);
-  AS_CHECK_ARG((int64_t)H * W <= 0x7FFFFFFF, "as_sgm_census: H * W = %lld overflows an int32 pixel index", (long long)H * W);
   AS_CHECK_ARG(((uintptr_t)census & 7) == 0 && ((uintptr_t)img & 3) == 0,
                "as_sgm_census: census must be 8-byte aligned and img 4-byte aligned");
   const int64_t n = (int64_t)B * H * W;
@@ -127,9 +119,7 @@ extern "C" int as_sgm_census(const float* img, int B, int C, int H, int W, uint6
   a.img = img; a.census = census; a.C = C; a.H = H; a.W = W;
   a.xtiles = as_div_up(W, SGM_CEN_W);
   a.tiles = (long)as_div_up(H, SGM_CEN_H) * a.xtiles;
-  const int64_t per_image = as_div_up(4 * SGM_GROUPS, B);
-  hipLaunchKernelGGL(sgm_census_kernel, dim3((unsigned)(a.tiles < per_image ? a.tiles : per_image), B), dim3(SGM_BLOCK), 0,
-                     (hipStream_t)stream, a);
+  hipLaunchKernelGGL(sgm_census_kernel, as_strided_grid(a.tiles, 4 * SGM_GROUPS, B), dim3(SGM_BLOCK), 0, (hipStream_t)stream, a);
   AS_CHECK_LAUNCH("as_sgm_census");
   return AS_OK;
 }
@@ -416,8 +406,7 @@ static __device__ inline void sgm_winner(const int (&s)[SGM_PER_LANE], int d0, i
 template <int G, bool VEC>
 __global__ __launch_bounds__(SGM_BLOCK) void sgm_select_kernel(SgmSelectArgs a) {
   __shared__ int s_count[2 * SGM_CODES];
-  if (threadIdx.x < 2 * SGM_CODES) s_count[threadIdx.x] = 0;
-  __syncthreads();
+  as_counts_begin(s_count, 2 * SGM_CODES);
   const int W = a.W, D = a.D;
   const long pixels = (long)a.H * W;
   const long image = blockIdx.y * pixels;
@@ -465,22 +454,14 @@ __global__ __launch_bounds__(SGM_BLOCK) void sgm_select_kernel(SgmSelectArgs a) 
 #pragma unroll
   for (int view = 0; view < 2; ++view)
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      int v = mine[view][c];
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-      if ((threadIdx.x & 63) == 0 && v) atomicAdd(&s_count[view * SGM_CODES + slot[c]], v);
-    }
-  __syncthreads();
-  if (threadIdx.x < 2 * SGM_CODES && s_count[threadIdx.x])
-    atomicAdd(a.counts + blockIdx.y * 2 * SGM_CODES + threadIdx.x, s_count[threadIdx.x]);
+    for (int c = 0; c < 3; ++c) as_counts_add(&s_count[view * SGM_CODES + slot[c]], mine[view][c]);
+  as_counts_flush(s_count, 2 * SGM_CODES, a.counts + blockIdx.y * 2 * SGM_CODES);
 }
 
 template <int G, bool VEC>
 static void sgm_select_launch(const SgmSelectArgs& a, int B, hipStream_t st) {
-  const int64_t per_block = SGM_BLOCK / G;
-  const int64_t blocks = ((int64_t)a.H * a.W + per_block - 1) / per_block, per_image = as_div_up(4 * SGM_GROUPS, B);
-  hipLaunchKernelGGL((sgm_select_kernel<G, VEC>), dim3((unsigned)(blocks < per_image ? blocks : per_image), B), dim3(SGM_BLOCK), 0, st, a);
+  const int64_t blocks = as_div_up((int64_t)a.H * a.W, SGM_BLOCK / G);
+  hipLaunchKernelGGL((sgm_select_kernel<G, VEC>), as_strided_grid(blocks, 4 * SGM_GROUPS, B), dim3(SGM_BLOCK), 0, st, a);
 }
 
 extern "C" int as_sgm_select(const void* workspace, int B, int H, int W, int D, int uniqueness, float fill, float* disp_l,
@@ -497,10 +478,7 @@ extern "C" int as_sgm_select(const void* workspace, int B, int H, int W, int D, 
                        {counts, (int64_t)B * 2 * SGM_CODES * 4}};
   AS_CHECK_ARG(as_disjoint(r, 1, 6), "as_sgm_select: an output may alias neither the workspace nor another output (overlapping ranges)");
   hipStream_t st = (hipStream_t)stream;
-  if (counts) {
-    as_zero_i32_enqueue(st, counts, B * 2 * SGM_CODES);
-    AS_CHECK_LAUNCH("as_sgm_select");
-  }
+  if (int rc = as_clear_counts("as_sgm_select", counts, B * 2 * SGM_CODES, st)) return rc;
   SgmSelectArgs a;
   a.S = (const uint16_t*)workspace;
   a.disp[0] = disp_l; a.disp[1] = disp_r; a.code[0] = code_l; a.code[1] = code_r; a.counts = counts;

@@ -77,6 +77,25 @@ def test_product_refuses_cpu_tensors():
     snet(x, torch.zeros(1, 32, 4, 4), torch.zeros(1, 32, 4, 4), "l")
 
 
+def test_shared_refusals_of_the_device_side_operators():
+  from adaptive_stereo import collect
+  with pytest.raises(RuntimeError, match=r"adaptive_stereo: Thing lives on the GPU \(got cpu\); there is no CPU path"):
+    collect.gpu_device("Thing", "cpu")
+  assert collect.gpu_device("Thing", "cuda:1") == torch.device("cuda:1")
+  cpu, code = torch.device("cpu"), torch.zeros(2, 1, 3, 8, dtype=torch.uint8)
+  collect.check_u8("op", "code", code, (2, 1, 3, 8), cpu)
+  for bad in (code.float(), code[..., ::2], code[:, :, :, :4].contiguous(), None):
+    with pytest.raises(RuntimeError, match=r"op: code must be a contiguous uint8 \(2, 1, 3, 8\) tensor on cpu \(got "):
+      collect.check_u8("op", "code", bad, (2, 1, 3, 8), cpu)
+  with pytest.raises(RuntimeError, match=r"op: x must be \(2, 1, 3, 8\) on cpu \(got \(2, 1, 3, 4\) on cpu\)"):
+    collect.check_shape("op", "x", torch.zeros(2, 1, 3, 4), (2, 1, 3, 8), cpu)
+  for size in ((0, 4, 1), (4, 4, 0)):
+    with pytest.raises(ValueError, match="MapOperator: size %d x 4, batch %d" % (size[0], size[2])):
+      collect.MapOperator(*size, device="cuda")
+  with pytest.raises(RuntimeError, match="no CPU path"):
+    collect.MapOperator(4, 4, 1, device="cpu")
+
+
 def test_parameter_gradients_go_to_both_sinks_or_to_two_fresh_tensors():
   """hip_ops._grad_dest decides for every backward kernel with a (weight, bias)-like gradient pair: both sinks and
   accumulate = 1, or two fresh tensors and accumulate = 0, never one of each; hip_ops._rmw records nothing outside a

@@ -19,20 +19,14 @@ from test_gpu_end_to_end import EPE_BAR, build
 from adaptive_stereo import consistency as cons
 from adaptive_stereo.pointcloud import DepthProjector, StereoCamera
 from adaptive_stereo.utils import synthetic as syn
+from guarded_buffers import DEV, same_bits
 from oracle import stereo_oracle as orc
 
-DEV = "cuda:0"
 B, H, W, K, MAXDISP = 2, 83, 150, 3, 100
 
 
 def _np_bits(a):
   return np.ascontiguousarray(a, dtype=np.float32).view(np.int32)
-
-
-def same_bits(got, want):
-  got = got.cpu().numpy()
-  assert got.shape == want.shape and got.dtype == want.dtype, (got.shape, want.shape, got.dtype, want.dtype)
-  return np.array_equal(_np_bits(got), _np_bits(want)) if got.dtype == np.float32 else np.array_equal(got, want)
 
 
 @pytest.fixture(scope="module")

@@ -25,23 +25,13 @@ from adaptive_stereo import consistency as cons
 from adaptive_stereo import disp_filter as dfm
 from adaptive_stereo.pointcloud import DepthProjector, StereoCamera
 from adaptive_stereo.utils import synthetic as syn
+from guarded_buffers import DEV, F, GUARD, SENTINEL, SENTINEL_I32, SENTINEL_U8, dev, same_bits
 
-DEV = "cuda:0"
-F = np.float32
-SENTINEL, SENTINEL_U8, SENTINEL_I32 = -7777.0, 0xA5, -7777
-GUARD = 64
 EDGE_OUTS = ("code", "valid", "jump", "counts")
 SPECKLE_OUTS = ("label", "size", "code", "valid", "counts")
 SHAPE_IDS = ["x".join(map(str, s)) for s in df.SHAPES]
 PATTERN_SHAPES = [(1, 2 * df.DF_ROWS + 1, df.DF_SPAN + 7), (2, df.DF_ROWS + 2, 2 * df.DF_WAVE + 3)]
 MODEL_FILTER = dict(tol_abs=0.5, tol_rel=0.0, max_diff=0.25, max_size=30)      # thresholds at which the model's maps show every code
-
-
-def same_bits(got, want):
-  """device tensor against a numpy array of the same dtype family, bit for bit"""
-  got = got.cpu().numpy()
-  assert got.shape == want.shape and got.dtype == want.dtype, (got.shape, want.shape, got.dtype, want.dtype)
-  return np.array_equal(got.view(np.uint32), want.view(np.uint32)) if got.dtype == F else np.array_equal(got, want)
 
 
 class Guarded(object):
@@ -90,10 +80,6 @@ def run_speckle(disp, code_in, max_diff, max_size, which=SPECKLE_OUTS):
   nat.call("as_disp_speckle", nat.ptr(disp), nat.ptr(code_in), B, H, W, max_diff, max_size,
            *([nat.ptr(g[k].view) if k in which else None for k in SPECKLE_OUTS] + [nat.stream()]))
   return _collect(g, SPECKLE_OUTS, which, (B, H, W))
-
-
-def dev(a):
-  return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
 
 def assert_same(got, want, names, what=""):

@@ -14,13 +14,8 @@ pytestmark = pytest.mark.gpu
 import lr_consistency_ref as lr
 from adaptive_stereo import _native as nat
 from adaptive_stereo import consistency as cons
+from guarded_buffers import DEV, SENTINEL, SENTINEL_I32, SENTINEL_U8, Guarded, same_bits
 
-DEV = "cuda:0"
-F = np.float32
-SENTINEL = -7777.0
-SENTINEL_U8 = 0xA5
-SENTINEL_I32 = -7777
-GUARD = 64
 FLOAT_OUTS = ("valid_l", "valid_r", "diff_l", "diff_r")
 ALL_OUTS = ("code_l", "code_r") + FLOAT_OUTS + ("counts",)
 SHAPE_IDS = ["x".join(map(str, s)) for s in lr.SHAPES]
@@ -29,28 +24,6 @@ FILL_SHAPES = lr.SHAPES + [(1, 10, 1242), (1, 10, 300)]             # + every pa
 
 def bits(t):
   return t.contiguous().view(torch.int32)
-
-
-def same_bits(got, want):
-  """device tensor against a numpy array of the same dtype family, bit for bit"""
-  got = got.cpu().numpy()
-  assert got.shape == want.shape and got.dtype == want.dtype, (got.shape, want.shape, got.dtype, want.dtype)
-  return np.array_equal(got.view(np.uint32), want.view(np.uint32)) if got.dtype == F else np.array_equal(got, want)
-
-
-class Guarded(object):
-  """`count` buffers of n elements each inside one sentinel-filled allocation, GUARD elements between and around them"""
-
-  def __init__(self, count, n, dtype=torch.float32, sentinel=SENTINEL):
-    self.n, self.count, self.sentinel = n, count, sentinel
-    self.raw = torch.full((count * (n + GUARD) + GUARD,), sentinel, dtype=dtype, device=DEV)
-    self.views = [self.raw[GUARD + i * (n + GUARD):GUARD + i * (n + GUARD) + n] for i in range(count)]
-
-  def guards_intact(self):
-    mask = torch.ones_like(self.raw, dtype=torch.bool)
-    for i in range(self.count):
-      mask[GUARD + i * (self.n + GUARD):GUARD + i * (self.n + GUARD) + self.n] = False
-    return bool((self.raw[mask] == self.sentinel).all())
 
 
 # ================================================================================================= as_lr_check
@@ -201,6 +174,9 @@ def test_refusals_set_the_error_and_launch_nothing():
     ("as_mirror_pair", (None, px, B, 1, H, W, o[0], o[1], s), "null"),
     ("as_mirror_pair", (px, px, B, 1, H, 0, o[0], o[1], s), "shape"),
     ("as_mirror_pair", (px, px, B, 1, H, W, o[0], o[0], s), "alias"),
+    ("as_mirror_pair", (o[0], o[1], B, 1, H, W, o[1], o[2], s), "alias"),       # left_batch over right
+    ("as_mirror_pair", (o[0], o[1], B, 1, H, W, o[2], o[0], s), "alias"),       # right_batch over left
+    ("as_mirror_pair", (o[0], o[1], B, 1, H, W, o[2], o[1], s), "alias"),       # right_batch over right
     ("as_flip_w", (px, 1, H, W, None, s), "null"),
     ("as_flip_w", (px, 0, H, W, o[0], s), "shape"),
     ("as_flip_w", (o[0], 1, H, W, o[0], s), "alias"),

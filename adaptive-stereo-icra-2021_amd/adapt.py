@@ -69,6 +69,21 @@ def append_trial_row(path, trial, step, metrics_adapt, metrics_train, gradient_u
     w.writerow({k: repr(v) if isinstance(v, float) else v for k, v in row.items()})
 
 
+def proxy_labeler_from_options(opt, stereo_net):
+  """The sgm.ProxyLabeler that --proxy_loss_weight > 0 asks for (None otherwise): at the resolution and batch size the step
+  runs at, over the network's own disparity range, which the matcher takes up to 256."""
+  if getattr(opt, "proxy_loss_weight", 0.0) <= 0.0:
+    if getattr(opt, "proxy_only", False) or getattr(opt, "ovs_metric", "photometric") == "proxy_epe":
+      raise ValueError("--proxy_only and --ovs_metric proxy_epe need --proxy_loss_weight above 0")
+    return None
+  from adaptive_stereo.sgm import ProxyLabeler
+  if stereo_net.maxdisp > 256:
+    raise ValueError("--proxy_loss_weight: the network's maxdisp %d is beyond the matcher's 256" % stereo_net.maxdisp)
+  s = opt.stereonet_input_scale
+  return ProxyLabeler(opt.height >> s, opt.width >> s, batch=opt.batch_size, maxdisp=stereo_net.maxdisp, paths=opt.proxy_paths,
+                      uniqueness=opt.proxy_uniqueness, max_size=opt.proxy_max_size)
+
+
 def adapt(opt, adapt_dataset=None, adapt_val_dataset=None, train_val_dataset=None, writer=None):
   """Reference adapt.py:187-443.  The datasets (map-style, of the StereoDataset sample dictionary) and ``writer`` (add_scalar /
   add_image) replace what the options would build.  Returns the AdaptationLoop."""
@@ -123,12 +138,15 @@ def adapt(opt, adapt_dataset=None, adapt_val_dataset=None, train_val_dataset=Non
     adapt_writer = _summary_writer(os.path.join(log_path, "adapt"))
     train_writer = _summary_writer(os.path.join(log_path, "train")) if adapt_writer is not None else None
 
+  labeler = proxy_labeler_from_options(opt, stereo_net)
   adapter = OnlineAdapter(feature_net, stereo_net, opt.height >> s, opt.width >> s, lr=opt.learning_rate,
                           clip_grad_norm=opt.clip_grad_norm, smoothness_weight=opt.smoothness_weight,
-                          fcs_ema_weight=opt.fcs_ema_weight)
+                          fcs_ema_weight=opt.fcs_ema_weight, proxy_labeler=labeler,
+                          proxy_loss_weight=getattr(opt, "proxy_loss_weight", 0.0), proxy_only=getattr(opt, "proxy_only", False))
   loop = AdaptationLoop(adapter, mode=opt.adapt_mode, ovs_buffer_size=opt.ovs_buffer_size, ovs_validate_hz=opt.ovs_validate_hz,
                         val_improve_retries=opt.val_improve_retries, ood_threshold=opt.ood_threshold,
-                        er_loss_weight=opt.er_loss_weight, captured=not getattr(opt, "no_capture", False))
+                        er_loss_weight=opt.er_loss_weight, captured=not getattr(opt, "no_capture", False),
+                        ovs_metric=getattr(opt, "ovs_metric", "photometric"))
 
   trials_path = os.path.join(log_path, "trials.csv")
   previous = read_trials(trials_path)
@@ -171,6 +189,10 @@ def adapt(opt, adapt_dataset=None, adapt_val_dataset=None, train_val_dataset=Non
         losses = {"Monodepth/total_loss": result["loss"], "fcs/raw": result["fcs"], "fcs/smoothed": result["fcs_smoothed"]}
         if result.get("replay_loss") is not None:
           losses["Replay/total_loss"] = result["replay_loss"]
+        if result.get("proxy_loss") is not None:
+          pixels = float(inputs[left_key].shape[0] * inputs[left_key].shape[-2] * inputs[left_key].shape[-1])
+          losses.update({"Proxy/loss": result["proxy_loss"], "Proxy/epe": result["proxy_epe"], "Proxy/bad": result["proxy_bad"],
+                         "Proxy/density": result["proxy_count"] / pixels})
         log_scalars(adapt_writer, metrics, losses, opt.batch_size / elapsed_this_batch, epoch, step)
         log_images(adapt_writer, inputs, outputs, step)
       step += 1

@@ -229,6 +229,9 @@ _SIGNATURES = {
   "as_khamis2_workspace": (c_i64, [c_i64]),
   "as_khamis2_fwd": (c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
   "as_khamis2_bwd": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_float, c_vp, c_vp, c_vp]),
+  "as_proxy_term_workspace": (c_i64, [c_i64]),
+  "as_proxy_term_fwd": (c_int, [c_vp, c_vp, c_vp, c_i64, c_float, c_vp, c_vp, c_vp]),
+  "as_proxy_term_bwd": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp]),
   "as_decode_rgb8": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp]),
   "as_decode_plane": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_vp,
                               c_vp]),

@@ -258,7 +258,14 @@ class OnlineAdapter(object):
 
   def __init__(self, feature_net, stereo_net, height, width, lr=5e-5, clip_grad_norm=True,
                smoothness_weight=1e-3, fcs_ema_weight=0.999, process_group=None, sync_bn=False,
-               overlap_features=True, force_data_parallel=False, pair_features=True, native_collectives=True):
+               overlap_features=True, force_data_parallel=False, pair_features=True, native_collectives=True,
+               proxy_labeler=None, proxy_loss_weight=0.0, proxy_only=False, proxy_bad_px=3.0):
+    """proxy_labeler (an sgm.ProxyLabeler of this adapter's height, width, batch and device) with proxy_loss_weight w > 0:
+    every train-mode forward runs the labeler's chain on the same pair and stream and back-propagates
+    loss + w * proxy (proxy_only: w * proxy alone; the photometric loss is still computed and reported: the OOD gate, the
+    reservoir and trials.csv use it).  proxy = hip_ops.ProxyTermFn: the Khamis loss against the matcher's disparity where
+    every stage of the labeler kept the pixel; proxy_bad_px: the error beyond which a labelled pixel counts as bad in
+    ``proxy_bad``.  Without a labeler (or with weight 0) nothing is enqueued that was not before."""
     self.feature_net, self.stereo_net = feature_net, stereo_net
     self.scale = stereo_net.input_scale
     self.coarse_scale = stereo_net.input_scale + stereo_net.k
@@ -305,6 +312,24 @@ class OnlineAdapter(object):
     # (FeatureExtractorNetwork.forward_pair); False: two passes, side by side on two streams (the round-2 arrangement)
     self.pair_features = pair_features
     self.infer_batched_features_max = 1 << 30     # pairs per call up to which inference batches left and right images
+    self.proxy_labeler, self.proxy_w = proxy_labeler, float(proxy_loss_weight)
+    self.proxy_only, self.proxy_bad_px = bool(proxy_only), float(proxy_bad_px)
+    if not self.proxy_w >= 0.0:
+      raise ValueError("OnlineAdapter: proxy_loss_weight %r must be a number and not negative" % (proxy_loss_weight,))
+    if not (self.proxy_bad_px >= 0.0 and self.proxy_bad_px != float("inf")):
+      raise ValueError("OnlineAdapter: proxy_bad_px %r must be finite and not negative" % (proxy_bad_px,))
+    if self.proxy_only and (proxy_labeler is None or self.proxy_w == 0.0):
+      raise ValueError("OnlineAdapter: proxy_only needs a proxy_labeler and a proxy_loss_weight above 0")
+    if proxy_labeler is None and self.proxy_w > 0.0:
+      raise ValueError("OnlineAdapter: proxy_loss_weight %r without a proxy_labeler" % (proxy_loss_weight,))
+    if proxy_labeler is not None:
+      if self.dp:
+        raise NotImplementedError("OnlineAdapter: a proxy_labeler in a data-parallel adapter: the proxy count would have to "
+                                  "join the step's all-reduce, which it does not")
+      m = proxy_labeler.matcher
+      if (m.H, m.W) != (int(height), int(width)) or m.buffers_device() != dev:
+        raise ValueError("OnlineAdapter: proxy_labeler of %d x %d on %s, the adapter is %d x %d on %s"
+                         % (m.H, m.W, m.buffers_device(), height, width, dev))
 
   # -- forward only: evaluate_model.py:52-60 / train.py:94-96 ------------------------------------
   @torch.no_grad()
@@ -382,6 +407,7 @@ class OnlineAdapter(object):
     return self._step_eager(left, right)
 
   def _forward_maps(self, left, right):
+    self._check_proxy_batch(left)
     if self.bn_sync is None:
       fl, fr = self._features_train(left, right)
     else:
@@ -393,8 +419,43 @@ class OnlineAdapter(object):
                                                                                 self.warper._width))
     # warp + monodepth loss + masked mean (adapt.py:78-86) as one autograd node: (mean, sum, valid count, warped, mask)
     mean, lsum, count, warped, _mask = hip_ops.MaskedPhotometricFn.apply(pred, left, right, self.sw)
+    proxy = self._proxy_term(pred, left, right)
     fcs_map = feature_contrast_mean(out["cost_volume_l/{}".format(self.coarse_scale)])
-    return (mean, lsum, count), fcs_map, out, warped
+    return (mean, lsum, count), fcs_map, out, warped, proxy
+
+  def _proxy_active(self):
+    return self.proxy_labeler is not None and self.proxy_w > 0.0
+
+  def _check_proxy_batch(self, left):
+    """Before anything of a step is enqueued: the labeler's buffers are fixed at its batch size."""
+    if self._proxy_active() and left.shape[0] != self.proxy_labeler.matcher.B:
+      raise ValueError("OnlineAdapter: a batch of %d pairs, the proxy_labeler was built for %d"
+                       % (left.shape[0], self.proxy_labeler.matcher.B))
+
+  def _proxy_term(self, pred, left, right):
+    """(proxy loss, out6) of hip_ops.ProxyTermFn on the labeler's chain over this pair, or None without one.  The chain is
+    the labeler's eager one on the current stream (under capture: nodes of the step's own graph, one stream, no fork; a
+    labeler that holds a graph of its own keeps it) and the node reads the matcher's disp_l and the filter's code where they
+    lie: the label map is not written."""
+    if not self._proxy_active():
+      return None
+    disp, code, _counts = self.proxy_labeler.chain(nat.f32c(left.detach()), nat.f32c(right.detach()))
+    return hip_ops.ProxyTermFn.apply(pred, disp, code, self.proxy_bad_px)
+
+  def _with_proxy(self, loss, proxy):
+    """What is back-propagated: loss + w * proxy, with proxy_only w * proxy alone."""
+    if proxy is None:
+      return loss
+    return self.proxy_w * proxy[0] if self.proxy_only else loss + self.proxy_w * proxy[0]
+
+  @staticmethod
+  def _proxy_results(proxy):
+    """proxy_loss, proxy_epe, proxy_bad, proxy_count: 0-d device tensors (views of out6, no read-back), None without a labeler."""
+    names = ("proxy_loss", "proxy_epe", "proxy_bad", "proxy_count")
+    if proxy is None:
+      return dict.fromkeys(names)
+    out6 = proxy[1]
+    return dict(zip(names, (out6[0], out6[3], out6[4], out6[5])))
 
   def _step_eager(self, left, right):
     self.feature_net.train(); self.stereo_net.train()
@@ -402,18 +463,20 @@ class OnlineAdapter(object):
     self.arena.zero_grads()
     # (multi-stream: two streams update the same gradient sinks / running statistics: keep order)
     with hip_ops.step_region(self.plan, self.bn_sync):
-      (loss, lsum, count), fcs_map, out, warped = self._forward_maps(left, right)
+      (loss, lsum, count), fcs_map, out, warped, proxy = self._forward_maps(left, right)
 
       if not self.dp:
         fcs = fcs_map.mean()
-        loss.backward()
+        self._with_proxy(loss, proxy).backward()
       else:
         loss, fcs = self._distributed_backward(lsum, count, fcs_map)
 
     self.optimizer.step(clip=self.clip)
     self._update_fcs_ema(fcs)
     out["left_warped/{}".format(self.scale)] = warped
-    return {"loss": loss.detach(), "fcs": fcs, "fcs_smoothed": self.fcs_smoothed, "outputs": out}
+    res = {"loss": loss.detach(), "fcs": fcs, "fcs_smoothed": self.fcs_smoothed, "outputs": out}
+    res.update(self._proxy_results(proxy))
+    return res
 
   def _update_fcs_ema(self, fcs):
     """FCS EMA (adapt.py:356-359): created on first use, then in place so that a captured graph keeps updating the same tensor."""
@@ -433,6 +496,8 @@ class OnlineAdapter(object):
     and the state machine must decide identically on every rank, and the reference's loss is the masked mean over the
     valid pixels of the whole batch (adapt.py:83), not a mean of per-rank means."""
     from .utils.loss_functions import khamis_robust_loss
+    if train:
+      self._check_proxy_batch(left)
     self.feature_net.train(train); self.stereo_net.train(train)
     if train:
       self.arena.rebind_grads()
@@ -448,14 +513,15 @@ class OnlineAdapter(object):
       out = self.stereo_net(left, fl, fr, "l", output_cost_volume=True)
       pred = out["pred_disp_l/{}".format(self.scale)]
       loss, lsum, count, warped, _mask = hip_ops.MaskedPhotometricFn.apply(pred, left, right, self.sw)
-      backprop = loss
+      proxy = self._proxy_term(pred, left, right) if train else None
+      backprop = self._with_proxy(loss, proxy)
       replay_loss = None
       if replay is not None:
         rl, rr, rgt = replay
         rfl, rfr = self._features_train(rl, rr) if two_streams else (self.feature_net(rl), self.feature_net(rr))
         rout = self.stereo_net(rl, rfl, rfr, "l", output_cost_volume=True)
         replay_loss = khamis_robust_loss(rout["pred_disp_l/{}".format(self.scale)], rgt)
-        backprop = loss + er_loss_weight * replay_loss
+        backprop = backprop + er_loss_weight * replay_loss
     fcs_map = feature_contrast_mean(out["cost_volume_l/{}".format(self.coarse_scale)])
     fcs = fcs_map.mean()
     dp_terms = None
@@ -483,9 +549,11 @@ class OnlineAdapter(object):
         dp_terms = (lsum, None, None, six[0])
     self._update_fcs_ema(fcs)
     out["left_warped/{}".format(self.scale)] = warped
-    return {"loss": loss.detach(), "replay_loss": None if replay_loss is None else replay_loss.detach(),
-            "backprop_loss": backprop, "dp_terms": dp_terms, "fcs": fcs, "fcs_smoothed": self.fcs_smoothed,
-            "outputs": out}
+    res = {"loss": loss.detach(), "replay_loss": None if replay_loss is None else replay_loss.detach(),
+           "backprop_loss": backprop, "dp_terms": dp_terms, "fcs": fcs, "fcs_smoothed": self.fcs_smoothed,
+           "outputs": out}
+    res.update(self._proxy_results(proxy))
+    return res
 
   def backward_update(self, result, gate=None):
     """backward + clip + Adam for a result of forward_loss(train=True) (adapt.py:381-394).  ``gate``: FusedClipAdam.step's.  Data parallel: every rank
@@ -524,6 +592,27 @@ class OnlineAdapter(object):
       loss = two[0] / two[1]
     self.feature_net.train(was_f); self.stereo_net.train(was_s)
     return float(loss)
+
+  @torch.no_grad()
+  def validation_proxy_epe(self, left, right):
+    """The mean |matcher - network| over the labelled pixels of one pair, in pixels: the eval-mode forward, the labeler's chain
+    on the pair, out6[3] of hip_ops.ProxyTermFn, one read-back.  A validation signal that does not rest on the photometric loss.
+    A pair on which the labeler keeps no pixel (proxy_count == 0) scores by its photometric loss, validation_loss's value,
+    instead: an empty label set says nothing about the network, and the 0.0 its mean would be reads as a perfect score, which
+    would pull the reservoir's average down and keep the state machine adapting on no evidence."""
+    if self.proxy_labeler is None:
+      raise RuntimeError("OnlineAdapter.validation_proxy_epe needs a proxy_labeler")
+    was_f, was_s = self.feature_net.training, self.stereo_net.training
+    self.feature_net.eval(); self.stereo_net.eval()
+    fl, fr = self._features_eval(left, right)
+    out = self.stereo_net(left, fl, fr, "l", output_cost_volume=True)
+    pred = out["pred_disp_l/{}".format(self.scale)]
+    loss = hip_ops.MaskedPhotometricFn.apply(pred, left, right, self.sw)[0]
+    disp, code, _counts = self.proxy_labeler.chain(nat.f32c(left.detach()), nat.f32c(right.detach()))
+    out6 = hip_ops.ProxyTermFn.apply(pred, disp, code, self.proxy_bad_px)[1]
+    self.feature_net.train(was_f); self.stereo_net.train(was_s)
+    photometric, epe, count = torch.stack([loss, out6[3], out6[5]]).tolist()       # the one read-back
+    return epe if count > 0 else photometric
 
   def close(self):
     """Releases the library's own RCCL communicator (collective: every rank calls it, before the process group goes)."""
@@ -587,7 +676,7 @@ class OnlineAdapter(object):
       self.arena.zero_grads()
       # bn_sync=None changes nothing here: capture() has refused cross-replica BatchNorm over torch.distributed collectives
       with hip_ops.step_region(self.plan, bn_sync=None):
-        (_, lsum, count), fcs_map, out, warped = self._forward_maps(left, right)
+        (_, lsum, count), fcs_map, out, warped, _ = self._forward_maps(left, right)
         self._dp_local_sums(lsum, count, fcs_map)
         self._dp_backward(lsum)
       return out, warped

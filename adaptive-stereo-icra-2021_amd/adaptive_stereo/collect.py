@@ -64,6 +64,10 @@ class MapOperator(object):
     self._buffers_on = t.device                              # with the index that `device` may lack
     return t
 
+  def buffers_device(self):
+    """The device the buffers live on, with the index that the ``device`` argument may lack."""
+    return self._buffers_on
+
   def _check_map(self, who, name, t, channels=1):
     check_f32(who, name, t, ((4,), "[B,%s,H,W]" % ("1" if channels == 1 else "C")))
     check_shape(who, name, t, (self.B, channels, self.H, self.W), self._buffers_on)

@@ -23,6 +23,7 @@ from .capture import refuse_nested, static_pair, warm_up_and_capture
 from .utils.stereo_reservoir import StereoReservoir
 
 MODES = ("NONSTOP", "VS", "ER", "VS+ER", "NONE")
+OVS_METRICS = ("photometric", "proxy_epe")
 
 
 class State(Enum):
@@ -176,6 +177,10 @@ class AdaptationLoop(object):
   ood_threshold       a pair is novel when the smoothed FCS is below it
   er_loss_weight      weight of the Khamis loss on the replayed training pair (ER modes)
   captured            the gated step (below); off, the loop is the host-side one and its results are unchanged
+  ovs_metric          "photometric": the reservoir is validated by OnlineAdapter.validation_loss (the reference's);
+                      "proxy_epe": by OnlineAdapter.validation_proxy_epe, the mean distance to the semi-global matcher's labels
+                      (needs an adapter with a proxy_labeler; a stored pair without a single label scores by its photometric
+                      loss: see there).  Either runs every ovs_validate_hz steps, where the loop synchronises anyway.
 
   captured=True.  An IN_PROGRESS step is forward_loss, as_adapt_gate, as_reservoir_store, backward_update with the gated
   optimizer: the same call sequence as the host loop, always including backward, with the update withheld on the device when the
@@ -191,9 +196,14 @@ class AdaptationLoop(object):
   In the ER modes the replay triple must be given on every step or on none (one graph).  Single GPU only."""
 
   def __init__(self, adapter, mode="NONSTOP", ovs_buffer_size=10, ovs_validate_hz=100, val_improve_retries=1,
-               ood_threshold=15.0, er_loss_weight=0.05, captured=False):
+               ood_threshold=15.0, er_loss_weight=0.05, captured=False, ovs_metric="photometric"):
     if mode not in MODES:
       raise ValueError("adapt_mode must be one of %s" % (MODES,))
+    if ovs_metric not in OVS_METRICS:
+      raise ValueError("ovs_metric must be one of %s" % (OVS_METRICS,))
+    if ovs_metric == "proxy_epe" and getattr(adapter, "proxy_labeler", None) is None:
+      raise ValueError("AdaptationLoop(ovs_metric=\"proxy_epe\") needs an adapter with a proxy_labeler")
+    self.ovs_metric = ovs_metric
     if captured and getattr(adapter, "dp", False):
       raise NotImplementedError("AdaptationLoop(captured=True) is single-GPU: a data-parallel adapter decides the gate on "
                                 "all-reduced scalars, which the captured step does not do; use captured=False")
@@ -220,6 +230,8 @@ class AdaptationLoop(object):
       self._adds_seen = 0
 
   def _validation_loss(self, left, right):
+    if self.ovs_metric == "proxy_epe":
+      return self.adapter.validation_proxy_epe(left, right)
     return self.adapter.validation_loss(left, right)
 
   def process(self, left, right, batch_idx, replay=None):

@@ -1783,6 +1783,40 @@ class KhamisLossFn(torch.autograd.Function):
     return g_pred, None
 
 
+class ProxyTermFn(torch.autograd.Function):
+  """(pred fp32, disp fp32, code uint8: the same shape; bad_px) -> (loss, out6): the Khamis loss of ``pred`` against the
+  matcher's ``disp`` over the pixels with code == 0 and disp > 0, read where sgm.ProxyLabeler leaves them (as_proxy_term_fwd).
+  out6 = [loss, max(count, 1), sum, mean |disp - pred|, share with |disp - pred| > bad_px, count]; not differentiable.  The
+  gradient goes to ``pred`` only.  ``disp`` and ``code`` are read in place: they must be contiguous and of their dtype."""
+
+  @staticmethod
+  def forward(ctx, pred, disp, code, bad_px):
+    pred = f32c(pred)
+    nat.require_gpu(disp, code)
+    if disp.dtype != torch.float32 or code.dtype != torch.uint8 or not (disp.is_contiguous() and code.is_contiguous()):
+      raise RuntimeError("ProxyTermFn: disp (%s) must be contiguous fp32 and code (%s) contiguous uint8" % (disp.dtype, code.dtype))
+    if not (pred.shape == disp.shape == code.shape) or disp.device != pred.device or code.device != pred.device:
+      raise RuntimeError("ProxyTermFn: pred %s, disp %s and code %s differ in shape or device"
+                         % (tuple(pred.shape), tuple(disp.shape), tuple(code.shape)))
+    n = pred.numel()
+    out6 = _empty(6, pred.device)
+    ws = _empty(nat.load().as_proxy_term_workspace(n), pred.device)
+    call("as_proxy_term_fwd", ptr(pred), ptr(disp), ptr(code), n, float(bad_px), ptr(out6), ptr(ws), stream())
+    ctx.save_for_backward(pred, disp, code, out6)
+    ctx.mark_non_differentiable(out6)
+    return out6[0].clone(), out6
+
+  @staticmethod
+  def backward(ctx, g, _g_out6):
+    pred, disp, code, out6 = ctx.saved_tensors
+    if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+      raise NotImplementedError("ProxyTermFn: the gradient goes to pred only")
+    g = f32c(g).reshape(1)
+    g_pred = torch.empty_like(pred)
+    call("as_proxy_term_bwd", ptr(pred), ptr(disp), ptr(code), ptr(g), ptr(out6), pred.numel(), ptr(g_pred), stream())
+    return g_pred, None, None, None
+
+
 # ----------------------------------------------------------------------------------------
 # supervised two-scale loss (train.py:215: khamis_robust_loss_multiscale with scales = [s, s + k])
 # ----------------------------------------------------------------------------------------

@@ -132,10 +132,25 @@ class ProxyLabeler(object):
     self._graph_result = None
     self._capture_origin = None
 
-  def _eager(self, left, right):
+  @torch.no_grad()
+  def chain(self, left, right):
+    """The chain without the label map, enqueued on the current stream whether or not this object holds a graph: matcher,
+    left-right check, speckle pass -> (disp_l, code, counts), views of the matcher's and the filter's buffers.  For a consumer that
+    reads the two where they lie (hip_ops.ProxyTermFn: a label iff code == 0 and disp_l > 0) and for a caller that is itself
+    being captured: the launches become nodes of ITS graph, on its stream, without a fork.  labels_buffer() is not written."""
+    who = "ProxyLabeler.chain"
+    self.matcher._check_image(who, "left", left)
+    self.matcher._check_image(who, "right", right)
+    res, filt = self._chain(left, right)
+    return res.disp_l, filt.code, filt.counts
+
+  def _chain(self, left, right):
     res = self.matcher(left, right, fill=float("nan"))
     chk = self.lrc.check(res.disp_l, res.disp_r, mirrored=False)
-    filt = self.filter.speckles(res.disp_l, chk.code_l)
+    return res, self.filter.speckles(res.disp_l, chk.code_l)
+
+  def _eager(self, left, right):
+    res, filt = self._chain(left, right)
     torch.eq(filt.code, 0, out=self._kept)
     torch.where(self._kept, res.disp_l, self._zero, out=self._labels)
     return self._labels, filt.code, filt.counts

@@ -15,6 +15,7 @@
 // nothing: 73 / 87 / 55 us on a box that runs the step 4 % slower.  Not kept.
 #include "photometric_dev.h"
 #pragma clang fp contract(off)
+#include "khamis.h"      // below the pragma: khamis_slope compiles uncontracted here, as the expression it replaced did
 
 // ---- deterministic per-image reductions --------------------------------------------------
 // partial[b][blk] (fp64) then a fixed-order finalize.
@@ -441,7 +442,6 @@ extern "C" int as_eval_metrics(const float* pred, const float* gt, int64_t n, fl
   return AS_OK;
 }
 
-#define MS_BLOCKS 512
 extern "C" int64_t as_masked_sum_workspace(int64_t n) { return n > 0 ? 4 * MS_BLOCKS : -1; }
 
 static int masked_sum_impl(const float* v, const uint8_t* mask, int64_t n, float* out2, float* workspace, void* stream, int with_mean);
@@ -475,9 +475,7 @@ __global__ __launch_bounds__(256) void khamis_fwd_kernel(const float* __restrict
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
     const float g = gt[i];
     if (g > 0.f) {
-      const float d = g - pred[i];
-      const float v = __fsub_rn(__fdiv_rn(__fsqrt_rn(__fadd_rn(__fmul_rn(d, d), 4.f)), 2.f), 1.f);
-      s += (double)v; c += 1.0;
+      s += (double)khamis_value(g, pred[i]); c += 1.0;
     }
   }
   s = wave_sum_d(s); c = wave_sum_d(c);
@@ -506,12 +504,7 @@ __global__ __launch_bounds__(256) void khamis_bwd_kernel(const float* __restrict
   const float scale = g_loss[0] / out2[1];
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
     const float g = gt[i];
-    float r = 0.f;
-    if (g > 0.f) {
-      const float d = g - pred[i];
-      r = -scale * d / (2.f * sqrtf(d * d + 4.f));
-    }
-    g_pred[i] = r;
+    g_pred[i] = g > 0.f ? khamis_slope(g, pred[i], scale) : 0.f;
   }
 }
 

@@ -5,20 +5,10 @@
 //   forward   ONE streaming pass over (gt, refined, up-sampled coarse) + the finalize: both losses, their sum, the count
 //   backward  ONE launch: workgroups [0, nadj) are the up-sampling adjoint with the coarse term's derivative formed where the
 //             adjoint loads it (never in HBM), the others write the refined map's element-wise derivative
-// Per-pixel value: the explicitly rounded fp32 chain of khamis_fwd_kernel (photometric.hip); sums: fixed-order fp64, two stages.
-#include "as_common.h"
+// Per-pixel value and slope: khamis.h, as khamis_fwd_kernel / khamis_bwd_kernel (photometric.hip); sums: fixed-order fp64, two stages.
+#include "khamis.h"
 
 #define K2_BLOCKS 512
-
-__device__ inline float khamis_value(float g, float p) {
-  const float d = g - p;
-  return __fsub_rn(__fdiv_rn(__fsqrt_rn(__fadd_rn(__fmul_rn(d, d), 4.f)), 2.f), 1.f);
-}
-// scale * d value / d p = -scale * (g - p) / (2 sqrt((g - p)^2 + 4)): the expression of khamis_bwd_kernel
-__device__ inline float khamis_slope(float g, float p, float scale) {
-  const float d = g - p;
-  return -scale * d / (2.f * sqrtf(d * d + 4.f));
-}
 
 __global__ __launch_bounds__(256) void khamis2_fwd_kernel(const float* __restrict__ pred0, const float* __restrict__ up,
                                                            const float* __restrict__ gt, long n, double* __restrict__ partial) {

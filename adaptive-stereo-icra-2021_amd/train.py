@@ -73,6 +73,15 @@ class TrainOptions(object):
     p.add_argument("--fcs_ema_weight", type=float, default=0.999)
     p.add_argument("--no_capture", action="store_true", default=False,
                    help="adapt.py: the host-side adaptation loop instead of the captured, device-gated one")
+    p.add_argument("--proxy_loss_weight", type=float, default=0.0,
+                   help="adapt.py: weight of the Khamis loss against semi-global-matching proxy labels (0: no matcher is built)")
+    p.add_argument("--proxy_only", action="store_true", default=False,
+                   help="adapt.py: back-propagate the proxy term alone (the photometric loss is still computed and reported)")
+    p.add_argument("--proxy_paths", type=int, default=8, choices=[4, 8], help="adapt.py: aggregation paths of the matcher")
+    p.add_argument("--proxy_uniqueness", type=int, default=5, help="adapt.py: the matcher's uniqueness margin in per cent")
+    p.add_argument("--proxy_max_size", type=int, default=200, help="adapt.py: largest speckle the label filter removes, in pixels")
+    p.add_argument("--ovs_metric", choices=["photometric", "proxy_epe"], default="photometric",
+                   help="adapt.py: what the online validation set is scored by (proxy_epe needs --proxy_loss_weight > 0)")
     self.parser = p
 
   def parse(self, args=None):

@@ -725,6 +725,34 @@ int as_khamis2_fwd(const float* pred0, const float* up, const float* gt, int64_t
 int as_khamis2_bwd(const float* pred0, const float* up, const float* gt, const float* g_out3, const float* out4,
                    int B, int H, int W, int h, int w, float gain, float* g_pred0, float* g_coarse, void* stream);
 
+/* ---- the proxy-label term of the adaptation loss — sgm.ProxyLabeler's outputs, read where they lie -------------
+ * pred: the network's disparity; disp: the matcher's left map (as_sgm_select's disp_l); code: the final code of the chain
+ * (as_disp_speckle's code).  fp32 / fp32 / uint8, n elements each, any shape; code may start at any byte.
+ * A pixel carries a label iff code[i] == 0 && disp[i] > 0.f: NaN, -0.0, 0.0, negatives and every non-zero code carry none.  This is
+ * the set where(code == 0, disp, 0) > 0, the valid set of as_khamis_fwd on the materialised labels.
+ * as_proxy_term_fwd: one streaming launch and a one-wave finalize; every output overwritten on every call, nothing read back.
+ *   v[i] = sqrt((disp - pred)^2 + 4) / 2 - 1 in fp32, the chain of as_khamis_fwd bit for bit (csrc/khamis.h: fma(d, d, 4), the
+ *     hardware's square root, fma(s, 0.5, -1));  e[i] = |disp[i] - pred[i]| (fp32, exact)
+ *   S = sum v, C = count, E = sum e, B = count(e > bad_px) over the labelled pixels: fp64, fixed order, two stages, with the
+ *     partition and the order of as_khamis_fwd (min(ceil(n / 256), 512) workgroups of 256, element i in lane i % 256 of
+ *     workgroup (i / 256) % workgroups, rising i per lane, the wave sum, the four waves, then one wave over the workgroups)
+ *   out6 = [ (float)S / (float)max(C, 1),  (float)max(C, 1),  (float)S,  (float)(E / max(C, 1)),  (float)(B / max(C, 1)),  (float)C ]
+ *   out6[0], out6[1] are bit for bit as_khamis_fwd's out2 on where(code == 0, disp, 0); without a label out6 = [0, 1, 0, 0, 0, 0].
+ *   A NaN of pred shows only where the pixel is labelled.  bad_px: finite, >= 0.
+ *   workspace: as_proxy_term_workspace(n) floats, 8-byte aligned (-1 for n <= 0).
+ * as_proxy_term_bwd: one launch.  g_pred[i] = *g_loss / out6[1] * d v[i] / d pred[i] = -scale * d / (2 sqrt(d^2 + 4)) with
+ *   d = disp - pred on the labelled pixels (the expression of as_khamis_bwd, compiled like it without contraction: every
+ *   operation rounded once, IEEE division and square root; bit for bit its result on the materialised labels),
+ *   exactly 0.f elsewhere.  g_loss: device scalar; out6: the forward's.  16 bytes per lane where pred, disp and g_pred are 16-byte
+ *   aligned, element by element otherwise and for the last n % 4.
+ * Refused (error set, nothing launched): a null pointer, n <= 0, an fp32 argument off 4 bytes, a workspace off 8 bytes, bad_px
+ * negative or not finite, out6 or workspace sharing a byte with an input or each other, g_pred sharing a byte with an input. */
+int64_t as_proxy_term_workspace(int64_t n);
+int as_proxy_term_fwd(const float* pred, const float* disp, const uint8_t* code, int64_t n, float bad_px, float* out6,
+                      float* workspace, void* stream);
+int as_proxy_term_bwd(const float* pred, const float* disp, const uint8_t* code, const float* g_loss, const float* out6,
+                      int64_t n, float* g_pred, void* stream);
+
 /* ---- dataset layer on the device ----------------------------------------------------
  * What datasets/stereo_dataset.py:49-96 and utils/dataset_utils.py:26-57 do per sample on the host (ToTensor,
  * flip_stereo_pair, crop, disparity decoding), over the raw decoded file contents uploaded once:

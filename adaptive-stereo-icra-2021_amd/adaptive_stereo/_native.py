@@ -264,6 +264,7 @@ _SIGNATURES = {
   "as_lr_fill": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp]),
   "as_disp_edge_check": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_float, c_float, c_vp, c_vp, c_vp, c_vp, c_vp]),
   "as_disp_speckle": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_float, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+  "as_disp_wmedian": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
   "as_rectify_map": (c_int, [_P(RectifyCamera), c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
   "as_rectify_pair": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, _P(RectifyCamera), _P(RectifyCamera), c_int, c_int, c_int, c_int,
                               c_float, c_vp, c_vp, c_vp]),

@@ -50,7 +50,7 @@ def int_in(who, name, value, lo, hi):
 
 class MapOperator(object):
   """What the operators on maps [batch,1,height,width] with buffers fixed at construction share (LeftRightConsistency,
-  DisparityFilter, SemiGlobalMatcher): the size, the device, the check of an argument against them and the shares of the codes."""
+  DisparityFilter, SemiGlobalMatcher, DisparitySmoother): the size, the device, the check of an argument against them and the shares of the codes."""
 
   def __init__(self, height, width, batch, device):
     who = type(self).__name__

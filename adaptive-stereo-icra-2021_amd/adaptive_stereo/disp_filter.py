@@ -105,15 +105,29 @@ class FilteredBothViewInference(consistency.BothViewInference):
   """BothViewInference with the post-filter in the chain: mirror, one forward pass over both views, the left-right check, the
   filter of the left view on what the check kept, the flip back, and the fill of the left view from the COMBINED code (rejected
   by the check, discontinuity or speckle).  ``__call__(left, right)`` -> (disp_l, disp_r, LRCheck, DispFilter, filled_l); after
-  capture() one graph replay."""
+  capture() one graph replay.
+
+  smooth_radius > 0 adds the weighted median of smooth.DisparitySmoother at the end of the chain (off by default: the chain and
+  its result are then what they were): on the left view, on what the filter kept (code_in = DispFilter.code), guided by the left
+  image when smooth_sigma is given (the plain median otherwise), filling rejected pixels with smooth_fill.  The result gains a
+  sixth element, its Smoothed; filled_l stays the row fill of the unsmoothed map."""
 
   def __init__(self, feature_net, stereo_net, height, width, batch=1, tol_abs=1.0, tol_rel=0.0, channels=3, edge_tol_abs=1.0,
-               edge_tol_rel=0.0, max_diff=1.0, max_size=200):
+               edge_tol_rel=0.0, max_diff=1.0, max_size=200, smooth_radius=0, smooth_sigma=None, smooth_fill=False):
     super().__init__(feature_net, stereo_net, height, width, batch, tol_abs, tol_rel, channels)
     self.filter = DisparityFilter(height, width, batch, edge_tol_abs, edge_tol_rel, max_diff, max_size, device=self.lrc.device)
+    self.smoother = None
+    if smooth_radius:
+      from .smooth import DisparitySmoother
+      self.smoother = DisparitySmoother(height, width, batch, radius=smooth_radius, sigma_color=smooth_sigma, channels=channels,
+                                        fill=smooth_fill, device=self.lrc.device)
 
   def _eager(self, left, right):
     disp_l, mirrored_r, chk = self._forward_and_check(left, right)
     filt = self.filter(disp_l, chk.code_l)
     consistency.flip_w(mirrored_r, out=self._disp_r)
-    return disp_l, self._disp_r, chk, filt, self.lrc.fill(disp_l, filt.code)
+    result = disp_l, self._disp_r, chk, filt, self.lrc.fill(disp_l, filt.code)
+    if self.smoother is None:
+      return result
+    guide = left if self.smoother.sigma_color is not None else None
+    return result + (self.smoother(disp_l, guide, filt.code),)

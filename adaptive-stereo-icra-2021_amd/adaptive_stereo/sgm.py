@@ -23,6 +23,7 @@ import torch
 
 from . import _native as nat
 from . import disp_filter
+from . import smooth
 from .capture import copy_unless_same, refuse_nested, warm_up_and_capture
 from .collect import MapOperator, check_f32, int_in
 from .consistency import LeftRightConsistency
@@ -111,16 +112,21 @@ class SemiGlobalMatcher(MapOperator):
 
 
 class ProxyLabeler(object):
-  """Sparse proxy labels from the matcher: SemiGlobalMatcher (fill NaN), LeftRightConsistency.check of its two views,
+  """Sparse proxy labels from the matcher: SemiGlobalMatcher (fill NaN), with median_radius > 0 the plain median of its two views
+  (smooth.DisparitySmoother; disp_l is then the smoothed map), LeftRightConsistency.check of the two views,
   DisparityFilter.speckles on what the check kept, labels = disp_l where the final code is 0 and 0.0 elsewhere.
   ``__call__(left, right)`` -> (labels [B,1,H,W], code uint8 [B,1,H,W], counts int32 [B,7]), views of buffers the next call
   overwrites.  A pixel the matcher rejected reaches the check as NaN and leaves it as code 4; whether it was out of view or not
   unique is in ``matcher``'s own code_l.  After capture() a call is a copy into the static inputs and one graph replay."""
 
   def __init__(self, height, width, batch=1, maxdisp=192, p1=10, p2=120, paths=8, uniqueness=5, channels=3, tol_abs=1.0,
-               tol_rel=0.0, max_diff=1.0, max_size=200, device="cuda"):
+               tol_rel=0.0, max_diff=1.0, max_size=200, median_radius=0, device="cuda"):
     self.matcher = SemiGlobalMatcher(height, width, batch, maxdisp, p1, p2, paths, uniqueness, channels, device)
     m = self.matcher
+    self.median_radius = int_in("ProxyLabeler", "median_radius", median_radius, 0, smooth.MAX_RADIUS)
+    # the plain median of either view in front of the check, each gated by the matcher's own code map (0: off, no launch)
+    self.medians = tuple(smooth.DisparitySmoother(m.H, m.W, m.B, radius=self.median_radius, device=m.device)
+                         for _ in range(2)) if self.median_radius else None
     self.lrc = LeftRightConsistency(m.H, m.W, m.B, tol_abs, tol_rel, device=m.device)
     self.filter = disp_filter.DisparityFilter(m.H, m.W, m.B, max_diff=max_diff, max_size=max_size, device=m.device)
     self._pair = torch.zeros(2 * m.B, m.C, m.H, m.W, dtype=torch.float32, device=m.device)      # static inputs [left; right]
@@ -146,6 +152,9 @@ class ProxyLabeler(object):
 
   def _chain(self, left, right):
     res = self.matcher(left, right, fill=float("nan"))
+    if self.medians is not None:                                         # a rejected pixel keeps its NaN: code 4 to the check
+      res = res._replace(disp_l=self.medians[0](res.disp_l, code_in=res.code_l).disp,
+                         disp_r=self.medians[1](res.disp_r, code_in=res.code_r).disp)
     chk = self.lrc.check(res.disp_l, res.disp_r, mirrored=False)
     return res, self.filter.speckles(res.disp_l, chk.code_l)
 

@@ -16,6 +16,11 @@
                    or on what --lr_check kept.  save: additionally filter_code_l/0 (uint8: the codes above, 5 discontinuity,
                    6 speckle), and with --lr_check pred_disp_l_filled/0 is filled from the combined code.  eval: additionally
                    the metrics over the ground-truth pixels the filter keeps, and the share of pixels kept.
+  --smooth_radius R  (not in the reference; default 0: off, nothing changes without it) --mode eval: additionally EPE and D1 of the
+                   left disparity after the weighted median of adaptive_stereo.smooth over a (2R + 1)^2 window, R 1 .. 7, beside
+                   the figures above.  --smooth_sigma S guides it by the left image (S in units of the image's range; without it
+                   the plain median); --smooth_fill lets it fill what --lr_check / --post_filter rejected, and the density (pixels
+                   with ground truth that hold a value, over pixels with ground truth) is reported too.
 
 Each mode is a function over a dataset-like iterable of {"color_l/0", "color_r/0", "gt_disp_l/0"} samples.
 """
@@ -163,6 +168,64 @@ def evaluate_post_filter(feature_net, stereo_net, val_loader, opt, lr_check=Fals
           "D1_all_5px": float(m[4]), "kept": share}
 
 
+class _Smoother(object):
+  """--smooth_radius: the DisparitySmoother of a batch shape (the last batch may be smaller), with the flags' settings."""
+
+  def __init__(self, opt):
+    self.radius, self.sigma, self.fill, self._smoothers = opt.smooth_radius, opt.smooth_sigma, opt.smooth_fill, {}
+
+  def __call__(self, disp, left, code_in=None):
+    """-> Smoothed of the left disparity [B,1,H,W], guided by `left` when --smooth_sigma is given, on what code_in kept"""
+    from adaptive_stereo.smooth import DisparitySmoother
+    key = tuple(disp.shape) + (left.shape[1],)
+    if key not in self._smoothers:
+      self._smoothers[key] = DisparitySmoother(key[2], key[3], batch=key[0], radius=self.radius, sigma_color=self.sigma,
+                                               channels=key[4], fill=self.fill, device=disp.device)
+    return self._smoothers[key](disp, left.float().contiguous() if self.sigma is not None else None, code_in)
+
+
+def evaluate_smoothing(feature_net, stereo_net, val_loader, opt):
+  """The figures of the left disparity before and after the weighted median, over the same pixels where nothing is filled:
+  {"raw": {...}, "smoothed": {...}}, each {"EPE", "D1_all_{2,3,4,5}px", "density"} over the ground-truth pixels that hold a value
+  (code 0; before: of --lr_check / --post_filter where given, else every usable pixel), "density" being those pixels over the
+  pixels with ground truth."""
+  feature_net.eval(); stereo_net.eval()
+  both = _BothViews(feature_net, stereo_net) if opt.lr_check else None
+  post = _PostFilter(opt) if opt.post_filter else None
+  smoother = _Smoother(opt)
+  rows = {"raw": [], "smoothed": []}
+  kept = {"raw": [], "smoothed": []}
+  labelled = []
+  with torch.no_grad():
+    for inputs in val_loader:
+      left, right = inputs["color_l/0"].cuda(), inputs["color_r/0"].cuda()
+      gt = inputs["gt_disp_l/0"].cuda().float()
+      if both is not None:
+        outputs, chk, _ = both(left, right)
+        code = chk.code_l
+      else:
+        outputs, code = process_batch(feature_net, stereo_net, left, right, opt), None
+      disp_l = outputs["pred_disp_l/0"].float().contiguous()
+      if post is not None:
+        code = post(disp_l, code).code
+      sm = smoother(disp_l, left, code)
+      usable = (disp_l >= 0) & ~torch.isinf(disp_l)
+      before = usable if code is None else usable & (code == 0)
+      has_gt = gt > 0
+      for name, disp, ok in (("raw", disp_l, before), ("smoothed", sm.disp, sm.code == 0)):
+        ok = ok & has_gt
+        rows[name].append(disparity_metrics(torch.where(ok, disp, torch.zeros_like(disp)), gt * ok.float()))
+        kept[name].append(ok.sum())
+      labelled.append(has_gt.sum())
+  figures = {}
+  n = int(torch.stack(labelled).sum()) if labelled else 0
+  for name in rows:
+    m = torch.stack(rows[name]).mean(dim=0).cpu() if rows[name] else torch.zeros(5)
+    figures[name] = {"EPE": float(m[0]), "D1_all_2px": float(m[1]), "D1_all_3px": float(m[2]), "D1_all_4px": float(m[3]),
+                     "D1_all_5px": float(m[4]), "density": float(torch.stack(kept[name]).sum()) / n if n else 0.0}
+  return figures
+
+
 def frame_epe(pred, gt):
   """Mean |pred - gt| over gt > 0 of one frame (evaluate_model.py:110), a Python float."""
   valid = gt > 0
@@ -239,6 +302,11 @@ def main(opt):
     if opt.post_filter:
       print("pixels the post-filter keeps%s:" % (" after the left-right check" if opt.lr_check else ""),
             evaluate_post_filter(feature_net, stereo_net, loader, opt, lr_check=opt.lr_check))
+    if opt.smooth_radius:
+      figures = evaluate_smoothing(feature_net, stereo_net, loader, opt)
+      what = "plain median" if opt.smooth_sigma is None else "weighted median (sigma %g)" % opt.smooth_sigma
+      print("before the %s of radius %d:" % (what, opt.smooth_radius), figures["raw"])
+      print("after the %s of radius %d%s:" % (what, opt.smooth_radius, ", filling" if opt.smooth_fill else ""), figures["smoothed"])
   else:
     raise NotImplementedError()
 
@@ -278,6 +346,12 @@ def make_parser():
   p.add_argument("--speckle_size", type=int, default=200, help="--post_filter: components of at most this many pixels are speckles")
   p.add_argument("--speckle_diff", type=float, default=1.0,
                  help="--post_filter: neighbours at most this far apart in disparity belong to one component")
+  p.add_argument("--smooth_radius", type=int, default=0,
+                 help="eval: also the figures after a weighted median over a (2R + 1)^2 window, 1 .. 7 (0: off)")
+  p.add_argument("--smooth_sigma", type=float, default=None,
+                 help="--smooth_radius: guide the median by the left image, in units of its range (default: the plain median)")
+  p.add_argument("--smooth_fill", action="store_true", default=False,
+                 help="--smooth_radius: fill rejected pixels from their window; the density is reported")
   return p
 
 

@@ -3,6 +3,8 @@ train.evaluate scores the network, so that the figures can be put side by side.
 
   python sgm_baseline.py --dataset_path ... --dataset_name KittiStereo2015 --split ... --subsplit val --height 320 --width 960
   python sgm_baseline.py ... --proxy          additionally the whole ProxyLabeler (left-right check, speckle filter)
+  python sgm_baseline.py ... --median 1       additionally the matcher's left view after a (2R + 1)^2 median (adaptive_stereo.smooth),
+                                              and with --proxy the labeler runs that median in front of its left-right check
 
 Printed and returned per stage: EPE and D1_all_{2,3,4,5}px of train.disparity_metrics over the pixels that have ground truth AND a
 kept code (the kernel counts gt > 0, so it is handed gt * kept), averaged per batch as train.evaluate averages, and "density":
@@ -14,6 +16,7 @@ import torch
 from torch.utils.data import DataLoader
 
 from adaptive_stereo.sgm import ProxyLabeler, SemiGlobalMatcher
+from adaptive_stereo.smooth import DisparitySmoother
 from evaluate_model import add_dataset_flags, make_dataset
 from train import disparity_metrics
 
@@ -41,11 +44,13 @@ class _Score(object):
 
 def evaluate_sgm(batches, opt):
   """batches: an iterable of collated samples {"color_l/0", "color_r/0", "gt_disp_l/0"} (a DataLoader, or a list of dicts).
-  -> {"sgm": figures} and, with opt.proxy, {"proxy": figures}.  The matchers are kept per batch shape (the last batch of a
-  split may be smaller)."""
-  matchers, scores = {}, {"sgm": _Score()}
+  -> {"sgm": figures} and, with opt.proxy, {"proxy": figures}, with opt.median {"sgm_median": figures}.  The matchers are kept per
+  batch shape (the last batch of a split may be smaller)."""
+  matchers, medians, scores = {}, {}, {"sgm": _Score()}
   if opt.proxy:
     scores["proxy"] = _Score()
+  if opt.median:
+    scores["sgm_median"] = _Score()
   params = dict(maxdisp=opt.maxdisp, p1=opt.p1, p2=opt.p2, paths=opt.paths, uniqueness=opt.uniqueness)
   with torch.no_grad():
     for inputs in batches:
@@ -55,7 +60,7 @@ def evaluate_sgm(batches, opt):
       if (B, C, H, W) not in matchers:
         if opt.proxy:
           labeler = ProxyLabeler(H, W, batch=B, channels=C, tol_abs=opt.lr_tol, max_diff=opt.speckle_diff, max_size=opt.speckle_size,
-                                 device=left.device, **params)
+                                 median_radius=opt.median, device=left.device, **params)
           matchers[(B, C, H, W)] = (labeler.matcher, labeler)
         else:
           matchers[(B, C, H, W)] = (SemiGlobalMatcher(H, W, batch=B, channels=C, device=left.device, **params), None)
@@ -68,6 +73,11 @@ def evaluate_sgm(batches, opt):
       else:
         res = matcher(left, right, fill=0.0)
         scores["sgm"].add(res.disp_l, res.code_l, gt)
+      if opt.median:                                                     # the matcher's left view, gated by its own code map
+        if (B, H, W) not in medians:
+          medians[(B, H, W)] = DisparitySmoother(H, W, batch=B, radius=opt.median, device=left.device)
+        sm = medians[(B, H, W)](res.disp_l, code_in=res.code_l)
+        scores["sgm_median"].add(torch.nan_to_num(sm.disp, nan=0.0), sm.code, gt)
   return {name: score.result() for name, score in scores.items()}
 
 
@@ -77,6 +87,8 @@ def main(opt):
   figures = evaluate_sgm(loader, opt)
   print("semi-global matching (%d paths, P1 %d, P2 %d, uniqueness %d, %d disparities):" % (opt.paths, opt.p1, opt.p2, opt.uniqueness,
                                                                                           opt.maxdisp), figures["sgm"])
+  if opt.median:
+    print("... after a %d x %d median:" % (2 * opt.median + 1, 2 * opt.median + 1), figures["sgm_median"])
   if opt.proxy:
     print("proxy labels (left-right check within %g px, speckles of at most %d pixels):" % (opt.lr_tol, opt.speckle_size),
           figures["proxy"])
@@ -96,6 +108,8 @@ def make_parser():
   p.add_argument("--speckle_size", type=int, default=200, help="--proxy: components of at most this many pixels are speckles")
   p.add_argument("--speckle_diff", type=float, default=1.0,
                  help="--proxy: neighbours at most this far apart in disparity belong to one component")
+  p.add_argument("--median", type=int, default=0,
+                 help="also the matcher after a (2R + 1)^2 median, 1 .. 7; with --proxy the labeler runs it before its check (0: off)")
   return p
 
 

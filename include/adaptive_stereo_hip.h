@@ -1109,6 +1109,39 @@ int as_disp_edge_check(const float* disp, const uint8_t* code_in, int B, int H, 
 int as_disp_speckle(const float* disp, const uint8_t* code_in, int B, int H, int W, float max_diff, int max_size, int32_t* label,
                     int32_t* size, uint8_t* code, float* valid, int32_t* counts, void* stream);
 
+/* ---- edge-aware disparity smoothing: the image-guided weighted median (csrc/disp_smooth.hip) ----
+ * The step that REPAIRS a map where the stages above only reject or fill along a row: the weighted median of Ma et al. (ICCV
+ * 2013) with integer weights from the guide image; with every weight 1 it is the plain median a classical matcher ends in.  The
+ * reference has nothing like it.  tests/disp_smooth_ref.py restates the contract in numpy.  Conventions as in the block above:
+ * dense fp32 [B][1][H][W] maps, uint8 codes of the same shape, USABLE as defined there, stream-ordered, nothing allocated, nothing
+ * read back (capturable).  One kernel launch (and the clearing launch when counts is given).
+ * AS_ERR_ARG before anything is enqueued: NULL disp or out, a non-positive extent, H * W > 2^31 - 1, B > 65535, a guide with C
+ * outside {1, 3}, a guide without a table or a table without a guide, radius outside 1 .. 7, fill outside {0, 1}, min_support < 1,
+ * disp, guide, weight_lut, out or counts not 4-byte aligned, an output that shares a byte with an input or with another output.
+ *
+ *   guide       (optional) fp32 [B][C][H][W], C 1 or 3, the network's image planes in [0, 1].  At every pixel and channel
+ *               g = (int)rintf(fminf(fmaxf(v, 0.f), 1.f) * 255.f): a NaN becomes 0, one rounding in the product, ties to even.
+ *   weight_lut  768 int32 on the device, with a guide only; each entry is clamped to 0 .. 65535 when it is read.
+ *               guide == NULL (and weight_lut == NULL): every weight is 1.
+ *   weight      of tap q seen from the centre p: w = lut[sum over c of |g_c(p) - g_c(q)|], an integer.
+ *   taps        the pixels q of the (2 * radius + 1)^2 window around p that lie in the image (no border replication) and are
+ *               usable (code_in NULL or 0 there, disp[q] >= 0 and != +inf).  The centre is a tap like any other if it is usable.
+ *               n = their number, Wt = the sum of their weights (at most 225 * 65535).
+ *   selection   the taps ordered by the bit pattern of their disparity read as signed int32 (the numeric order of usable
+ *               values, -0.0 before +0.0); m(p) = the disparity of the first tap in that order at which
+ *               2 * (cumulative weight) >= Wt.  Equal weights and even n: the LOWER median.
+ *   per pixel   p usable and Wt > 0: out = m(p).  p usable and Wt == 0: out = disp[p].
+ *               p not usable, fill == 1, n >= min_support and Wt > 0: out = m(p), code 0: FILLED.
+ *               p not usable otherwise: out = the bits of disp[p] (a NaN keeps its payload); code = code_in[p] where that is
+ *               non-zero (codes above 6 included), else 4.
+ *   out         (required) fp32; always the bits of one input disparity.
+ *   code        (optional) uint8: 0 wherever out holds a kept or a filled value.
+ *   counts      (optional) int32 [B][4], OVERWRITTEN: usable and bits unchanged, usable and bits changed, filled, still rejected;
+ *               the four sum to H * W per image.
+ * The result is a pure function of the inputs, bit-identical from run to run.  The kernel works on tiles of 16 rows x 64 columns. */
+int as_disp_wmedian(const float* disp, const uint8_t* code_in, const float* guide, int C, const int32_t* weight_lut, int B, int H,
+                    int W, int radius, int fill, int min_support, float* out, uint8_t* code, int32_t* counts, void* stream);
+
 /* ---- stereo rectification of raw camera pairs (csrc/rectify.hip) ----
  * The stage in front of the network for a rig, or a data set, whose images are NOT rectified: undistortion and the rectifying
  * rotation as one bilinear gather per output pixel, what a host pipeline does with cv2.initUndistortRectifyMap + cv2.remap.
